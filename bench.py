@@ -10,7 +10,14 @@ device->host read of the per-image counts the call ends with.  val.py hands the 
 beyond the 256 MB Infinity Cache): `ms_per_step` is the cold-cache number; `warm` reports the same loop on one tensor.
 Data is synthetic (tests/synth.py: S-pred), weights do not exist on this path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times exactly K steps, writes the outputs of the last timed step when --dump-outputs is
+given, and prints the result line (metric, value, unit, higher_is_better, dtype, ms_per_step, config, build).  Everything
+else the line can carry (the repeated timing windows, the per-stage and per-kernel figures, the 100k NMS regimes and the
+roofline, the other shapes, the CPU baseline) is measured only with --full.
+--dump-outputs DIR: the detections of the last timed step, one (n, 7) float32 array per image [x y l s theta conf cls], as
+DIR/detections_<image>.npy (<image> = rank * 16 + index in the batch).  The inputs are seeded: the same arguments give the
+same tensors from run to run.
 N > 1: one rank per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE set, the way the driver starts it) the process IS a
 rank; started plainly with --gpus N > 1 it re-executes itself under `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1` (the reference's multi-GPU entry is a launcher too: sh/ddp_train.sh:1,
@@ -20,11 +27,11 @@ images/s; `n_gpus` = dist.get_world_size(), `rccl_ranks` = the ranks that met at
 --dry-run: the launcher / rank plumbing alone on the CPU (gloo), no GPU work -- what the CPU test exercises.
 
 The timed K steps run with HIP events around the step's dominant kernel (the persistent NMS kernel; `obb_profile_enable(2)`: two
-event records per step on the kernels' stream); `ms_per_step_with_all_stage_events` is the same K steps with events around all
-five stages (ten records, ~30 us per step: what `stages_ms` / `kernels` list for the other stages), and
+event records per step on the kernels' stream); with --full, `ms_per_step_with_all_stage_events` is the same K steps with events
+around all five stages (ten records, ~30 us per step: what `stages_ms` / `kernels` list for the other stages), and
 `ms_per_step_without_stage_events` the same K steps without any.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      BASELINE.json's target figure: rotated NMS at N = 100k candidates, SURVEY.md section 8d's algorithmic bytes
                 bytes_nms(N) = 24N + 8N + 8N*ceil(N/64) over the time of the WHOLE call (sort + prep + the persistent
                 kernel; HIP events on the stream the kernels run on).  Reported for the WORST of the two regimes that
@@ -195,6 +202,16 @@ def provenance(_lib, L):
             "torch": torch.__version__, "hip": getattr(torch.version, "hip", None)}
 
 
+def dump_outputs(path, dets, first_image):
+    """The detections of one step (a list of (n, 7) tensors, one per image) -> path/detections_<image>.npy, float32 (float64 kept)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for i, d in enumerate(dets):
+        d = d.detach().cpu()
+        d = d.double() if d.dtype == torch.float64 else d.float()
+        np.save(os.path.join(path, f"detections_{first_image + i:03d}.npy"), d.numpy())
+
+
 def host_cpu_budget():
     """CPUs this process may really use: min(visible cores, the cgroup's CPU quota) -- cpu.max (cgroup v2) or cfs_quota_us / cfs_period_us."""
     n = os.cpu_count() or 1
@@ -282,10 +299,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline step + the 100k NMS regimes")
+    ap.add_argument("--full", action="store_true", help="also measure everything besides the headline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the detections of the last timed step as DIR/detections_<image>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baseline and next_rows")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the headline step + the 100k NMS regimes")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rank plumbing only, on the CPU with gloo")
-    ap.add_argument("--nms-n", type=int, default=100000)
+    ap.add_argument("--nms-n", type=int, default=100000, help="with --full: candidates of the nms_100k regimes")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -354,21 +373,54 @@ def main():
     for i in range(max(args.warmup, ROTATE)):
         out = non_max_suppression_obb(preds[i % ROTATE], **kw)
     barrier()
-    # THE timed region: K steps with HIP events around the step's dominant kernel only (the persistent NMS kernel: two records per
-    # step on the kernels' own stream; recording all five stages costs ten records = ~30 us of a 0.2 ms step)
+    # THE timed region: EXACTLY K steps, barrier + synchronize on both sides, with HIP events around the step's dominant kernel only
+    # (the persistent NMS kernel: two records per step on the kernels' own stream; recording all five stages costs ten records =
+    # ~30 us of a 0.2 ms step).  `ms_per_step` / `value` are this window's.
     # (one window of K x 0.14 ms is a 3 ms measurement -- one scheduler hiccup moves `value` by more than the
-    #  box-to-box spread.  The window of EXACTLY K steps, barrier + synchronize on both sides, is repeated WINDOWS times back to back;
-    #  `ms_per_step` / `value` are the MEDIAN window's, the others are reported next to it.)
+    #  box-to-box spread.  With --full the window is repeated WINDOWS - 1 more times back to back and `timed_windows` reports all of
+    #  them with their median.)
     L.obb_profile_enable(2)
     win_dt = []
-    for _w in range(WINDOWS):
-        t0 = time.perf_counter()
-        for i in range(args.steps):
-            out = non_max_suppression_obb(preds[i % ROTATE], **kw)
-        barrier()
-        win_dt.append(time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        out = non_max_suppression_obb(preds[i % ROTATE], **kw)
+    barrier()
+    win_dt.append(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank * bs)
+    if args.full:
+        for _w in range(WINDOWS - 1):
+            barrier()
+            t0 = time.perf_counter()
+            for i in range(args.steps):
+                out = non_max_suppression_obb(preds[i % ROTATE], **kw)
+            barrier()
+            win_dt.append(time.perf_counter() - t0)
     ms_sum_t, cnts_t = collect_profile(L)
     L.obb_profile_enable(0)
+    win_dt = [shard.max_over_ranks(w, device=dev) for w in win_dt]      # a window is as slow as its slowest rank
+    dt = win_dt[0]
+    ms_per_step = dt / args.steps * 1e3
+    value = world * bs * args.steps / dt
+    line = {
+        "metric": METRIC,
+        "value": round(value, 2), "unit": "img/s", "n_gpus": dist.get_world_size() if dist is not None else 1, "rccl_ranks": rccl_ranks,
+        "steps": args.steps, "warmup": args.warmup, "build": provenance(_lib, L),
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f16", "data": "synthetic",
+        "config": {"workload": f"DOTAv1.5 1024^2 bs16 (BASELINE metric; configs[1] thresholds): yolov5 OBB head output (16,64512,201) fp16, "
+                               f"{ROTATE} distinct tensors rotated (cold: {ROTATE * bs * A * no * 2 / 1e9:.2f} GB working set) -> non_max_suppression_obb "
+                               "(conf .25, iou .45, multi_label, max_det 1500), val.py --task speed hot path = dt[2] of val.py",
+                   "global_batch": bs * world, "anchors_per_image": A, "nc": nc,
+                   "detections_per_batch": sum(int(o.shape[0]) for o in out),
+                   "parallelism": f"dp{world} (images sharded, no data-path collective)"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # the same K steps with events around every stage: the per-stage figures of `stages_ms` / `kernels` (the NMS kernel's own figure
     # stays the one measured inside the timed region above)
     barrier()
@@ -400,13 +452,10 @@ def main():
     ms_warm = shard.max_over_ranks(time.perf_counter() - t0, device=dev) / args.steps * 1e3
     ms_sum_w, cnts_w = collect_profile(L)
     L.obb_profile_enable(0)
-    win_dt = [shard.max_over_ranks(w, device=dev) for w in win_dt]      # a window is as slow as its slowest rank
-    dt = sorted(win_dt)[len(win_dt) // 2]
-    ms_per_step = dt / args.steps * 1e3
     windows_obj = {"n": WINDOWS, "steps_each": args.steps, "ms_per_step": [round(w / args.steps * 1e3, 4) for w in win_dt],
-                   "median": round(ms_per_step, 4), "min": round(min(win_dt) / args.steps * 1e3, 4), "max": round(max(win_dt) / args.steps * 1e3, 4),
-                   "note": "every window: exactly `steps` steps between barrier + synchronize; value / ms_per_step = the median window"}
-    value = world * bs * args.steps / dt
+                   "median": round(sorted(win_dt)[len(win_dt) // 2] / args.steps * 1e3, 4),
+                   "min": round(min(win_dt) / args.steps * 1e3, 4), "max": round(max(win_dt) / args.steps * 1e3, 4),
+                   "note": "every window: exactly `steps` steps between barrier + synchronize; value / ms_per_step = the first window"}
 
     # the step's kernels, measured with HIP events inside the timed region (cold: rotating tensors; warm: one tensor)
     dec_ms = ms_sum[0] / max(1, cnts[0])
@@ -945,18 +994,10 @@ def main():
             cpu["error"] = str(e)
 
     if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": round(value, 2), "unit": "img/s", "n_gpus": dist.get_world_size() if dist is not None else 1, "rccl_ranks": rccl_ranks,
-            "steps": args.steps, "warmup": args.warmup, "build": provenance(_lib, L),
-            "ms_per_step": round(ms_per_step, 4), "timed_windows": windows_obj, "ms_per_step_with_all_stage_events": round(ms_all_events, 4), "ms_per_step_without_stage_events": round(ms_plain, 4),
-            "ms_per_step_one_tensor_warm": round(ms_warm, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f16", "data": "synthetic",
-            "config": {"workload": f"DOTAv1.5 1024^2 bs16 (BASELINE metric; configs[1] thresholds): yolov5 OBB head output (16,64512,201) fp16, "
-                                   f"{ROTATE} distinct tensors rotated (cold: {ROTATE * bs * A * no * 2 / 1e9:.2f} GB working set) -> non_max_suppression_obb "
-                                   "(conf .25, iou .45, multi_label, max_det 1500), val.py --task speed hot path = dt[2] of val.py",
-                       "global_batch": bs * world, "anchors_per_image": A, "nc": nc, "detections_per_batch": n_det,
-                       "parallelism": f"dp{world} (images sharded, no data-path collective)"},
+        line["config"]["detections_per_batch"] = n_det
+        line.update({
+            "timed_windows": windows_obj, "ms_per_step_with_all_stage_events": round(ms_all_events, 4), "ms_per_step_without_stage_events": round(ms_plain, 4),
+            "ms_per_step_one_tensor_warm": round(ms_warm, 4),
             "stages_ms": stages, "stages_ms_one_tensor_warm": stages_warm,
             # the roofline target of BASELINE.json's north_star: rotated NMS at 100k candidates (configs[3] stress),
             # SURVEY 8d formula over the whole call, the WORSE of clustered-K300 and clustered-K300 + 18 class offsets
@@ -997,7 +1038,7 @@ def main():
             "cpu_baseline": cpu,
             "parity_unpinned": ["poly2rbox against cv2.minAreaRect (utils/rboxs_utils.py:39-81: OpenCV is not in this image; without it the minimum-area rectangle is computed natively and the function is property-tested, tests/test_poly2rbox_props.py)",
                                 "OBB mAP@0.5 within 0.1 of the reference (DOTA_devkit/dota_evaluation_task1.py:320: no weights / dataset offline)"],
-        }
+        })
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -15,8 +15,8 @@ timeout 1800 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
 db() { find $1 -name '*.db' | head -1; }
 rm -rf /tmp/p_bench /tmp/p_kt /tmp/p_fetch /tmp/p_write
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p_bench -o bench -- python bench.py --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_prof.log 2>&1
-python tools/rocpd_summary.py "$(db /tmp/p_bench)" "rocprofv3 --kernel-trace --stats -- python bench.py --steps 50 --warmup 5 --no-cpu-baseline" > $O/bench_kernel_stats.md 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p_bench -o bench -- python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_prof.log 2>&1
+python tools/rocpd_summary.py "$(db /tmp/p_bench)" "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline" > $O/bench_kernel_stats.md 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p_kt -o kt -- python tools/prof_kernels.py > $O/kt.log 2>&1
 python tools/rocpd_summary.py "$(db /tmp/p_kt)" "rocprofv3 --kernel-trace --stats -- python tools/prof_kernels.py" > $O/kernel_stats.md 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/p_fetch -o fetch -- python tools/prof_kernels.py > $O/fetch.log 2>&1
@@ -55,6 +55,6 @@ fi
 timeout 400 python tools/trace_valbuckets.py 5 0 > $O/vb_compiled.log 2>&1
 grep -E "nr_throttled|throttled_usec" /sys/fs/cgroup/cpu.stat > $O/cgroup_after_compiled.txt 2>/dev/null
 timeout 300 python tools/time_valtail.py > $O/valtail.txt 2>&1
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 OBB_NMS_PHASE_PROF=1 timeout 300 python tools/prof_regimes.py > $O/nms_phases.txt 2>&1
 tail -3 $O/pytest_gpu.log; cat $O/smoke.log | tail -2; cut -c1-400 $O/bench.json
