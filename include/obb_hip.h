@@ -70,17 +70,15 @@ int obb_profile_collect(double* ms_sum_host, int64_t* count_host, int n_stages);
  *                           class reported (kept boxes, independent slabs, device time of either path)
  *   OBB_NMS_MK_XLDS=0 | 1   phase kernels: the cross probe on the chunk's table in global memory (0) or on a table of the kept rows in
  *                           every workgroup's LDS (1); default: 1 where the previous call kept <= 6144 boxes
- *   OBB_NMS_MK_NOFULL=0     phase kernels: the decide kernels run the IoU-interval stage in front of the exact clip again (default: the
- *                           pending pairs go straight to the clip)
  *   OBB_NMS_SELF_SORT=0|1|2 obb_non_max_suppression_obb* with the small-segment NMS kernel (expected_cand bits 32..60) and out_packed = 0:
  *                           0 = the per-image sort kernel in front of it, 1 = self-sorting segments (csrc/nmsobb_impl.h: SmallSelfSort --
  *                           no sort launch, two launches per call) where the sort kernel would hand out no helper workgroups,
  *                           2 = default: self-sorting segments wherever they are possible
  *   OBB_NMS_SMALL_HELPERS=n small-segment NMS kernel behind the sort kernel: helper workgroups that share large segments (0: none)
- * Read once per process, tests only: OBB_NMS_MK_STEPS (enqueued steps), OBB_NMS_MK_PEND (pending-list capacity), OBB_NMS_MK_CHUNK
- * (first chunk): they force the hand-overs to the persistent kernel that tests/test_nms_mk_gpu.py checks.
- * Development builds only (make DEV=1; ignored otherwise): the A/B switches OBB_NMS_NO_GRID, OBB_NMS_NO_SLABS, OBB_NO_CLASS_SEG,
- * OBB_NO_LDS_SORT, OBB_NMS_GROUP_AFTER_CUT, OBB_NMS_CHUNK*, OBB_NMS_GROW, OBB_NMS_SLAB_CAP, OBB_GRID_FINE, OBB_LOSS_NT. */
+ * Read once per process, tests only: OBB_NMS_MK_STEPS (enqueued steps), OBB_NMS_MK_PEND (pending-list capacity): they force the
+ * hand-overs to the persistent kernel that tests/test_nms_mk_gpu.py checks.
+ * Compile-time diagnostics (-D, csrc/): OBB_SMALL_TRACE, OBB_SORT_TRACE (per-workgroup time stamps printed by the kernels),
+ * OBB_NMS_FULL_FENCE (a full fence where the kernels read other workgroups' results: a check for stale reads). */
 
 /* ------------------------------------------------------------------ NMS ------------------------------ */
 

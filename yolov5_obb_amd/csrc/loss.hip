@@ -396,8 +396,8 @@ template <> struct Vec16<__half> { static constexpr int V = 8; };
 
 typedef unsigned int loss_u32x4 __attribute__((ext_vector_type(4)));
 
-// NTS: the gradient tensor is written once and read much later (the conv's backward): streaming stores
-template <typename T, bool NTS>
+// The gradient tensor is written once and read much later (the conv's backward): streaming stores
+template <typename T>
 __global__ __launch_bounds__(256) void k_loss_bwd_dense(const LossDev* __restrict__ dp) {
   constexpr int V = Vec16<T>::V;
   const LossDev& d = *dp;
@@ -438,8 +438,7 @@ __global__ __launch_bounds__(256) void k_loss_bwd_dense(const LossDev* __restric
           if constexpr (V == 4) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (j == 0) v.x = val; else if (j == 1) v.y = val; else if (j == 2) v.z = val; else if (j == 3) v.w = val;
-            if constexpr (NTS) __builtin_nontemporal_store(__builtin_bit_cast(loss_u32x4, v), reinterpret_cast<loss_u32x4*>(gb + i0));
-            else *reinterpret_cast<float4*>(gb + i0) = v;
+            __builtin_nontemporal_store(__builtin_bit_cast(loss_u32x4, v), reinterpret_cast<loss_u32x4*>(gb + i0));
           } else {
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
             if (j >= 0) {
@@ -447,8 +446,7 @@ __global__ __launch_bounds__(256) void k_loss_bwd_dense(const LossDev* __restric
               const int q = j >> 1;
               if (q == 0) v.x = h; else if (q == 1) v.y = h; else if (q == 2) v.z = h; else v.w = h;
             }
-            if constexpr (NTS) __builtin_nontemporal_store(__builtin_bit_cast(loss_u32x4, v), reinterpret_cast<loss_u32x4*>(gb + i0));
-            else *reinterpret_cast<uint4*>(gb + i0) = v;
+            __builtin_nontemporal_store(__builtin_bit_cast(loss_u32x4, v), reinterpret_cast<loss_u32x4*>(gb + i0));
           }
         } else {
           for (int q = 0; q < V && i0 + q < nel; q++) st_from_float<T>(gb + i0 + q, q == j ? val : 0.f);
@@ -700,9 +698,8 @@ int obb_loss_backward(const obb_loss_config* cfg, const void* const* p_levels_ho
   }
   k_loss_setup<<<1, 256, 0, st>>>(d, cv.dev);
   dim3 gd(2048, cfg->nl);
-  static const int nts = obb_dev_switch("OBB_LOSS_NT", 1) != 0 ? 1 : 0;      // 0: plain stores (development builds: measurements)
-  if (dtype == 0) { if (nts) k_loss_bwd_dense<float, true><<<gd, 256, 0, st>>>(cv.dev); else k_loss_bwd_dense<float, false><<<gd, 256, 0, st>>>(cv.dev); }
-  else { if (nts) k_loss_bwd_dense<__half, true><<<gd, 256, 0, st>>>(cv.dev); else k_loss_bwd_dense<__half, false><<<gd, 256, 0, st>>>(cv.dev); }
+  if (dtype == 0) k_loss_bwd_dense<float><<<gd, 256, 0, st>>>(cv.dev);
+  else k_loss_bwd_dense<__half><<<gd, 256, 0, st>>>(cv.dev);
   if (d.cap > 0) {
     if (dtype == 0) k_loss_entries_bwd<float><<<entry_grid(d), 256, 0, st>>>(cv.dev);
     else k_loss_entries_bwd<__half><<<entry_grid(d), 256, 0, st>>>(cv.dev);

@@ -430,24 +430,11 @@ __global__ void k_finalize(const int* __restrict__ keep_cnt, const int* __restri
 // ---------------------------------------------------------------- workspace
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
-// Chunk capacities: the first chunk has OBB_NMS_CHUNK boxes (default 2048), later chunks double up to
-// OBB_NMS_CHUNK_MAX (default 8192 for a single list, 2048 per segment for batches: the edge list is sized for
-// the worst case cap*(cap-1)/2 per segment).
-static int env_int(const char* name, int dflt, int lo, int hi) {
-  int v = obb_dev_switch(name, dflt);
-  if (v < lo) v = lo;
-  if (v > hi) v = hi;
-  return (v + 63) / 64 * 64;
-}
-static int cap_first() { static const int c = env_int("OBB_NMS_CHUNK", 2048, 64, 8192); return c; }   // clipped to cap_max in the kernel
-// (the edge list of a team is sized for the worst case cap*(cap-1)/2 of one chunk: 134 MB at 8192, 8.4 MB at 2048,
-//  2 MB at 1024 -- times the number of teams)
-static int cap_max(int64_t nseg) {
-  static const int c1 = env_int("OBB_NMS_CHUNK_MAX", 8192, 64, 16384);
-  static const int cb = env_int("OBB_NMS_CHUNK_MAX_BATCHED", 2048, 64, 16384);
-  static const int cm = env_int("OBB_NMS_CHUNK_MAX_MANY", 1024, 64, 16384);
-  return nseg == 1 ? c1 : (nseg <= 64 ? cb : cm);
-}
+// Chunk capacities: the first chunk has 2048 boxes, later chunks double up to 8192 for a single list, 2048 per segment for
+// batches of up to 64 segments and 1024 beyond.  (The edge list of a team is sized for the worst case cap*(cap-1)/2 of one
+// chunk: 134 MB at 8192, 8.4 MB at 2048, 2 MB at 1024 -- times the number of teams.)
+constexpr int kCapFirst = 2048;     // clipped to cap_max in the kernel
+static int cap_max(int64_t nseg) { return nseg == 1 ? 8192 : (nseg <= 64 ? 2048 : 1024); }
 
 constexpr int kMaxTeams = 1024;     // >= number of CUs of any gfx950 part
 
@@ -472,14 +459,14 @@ struct Carve {
 
 // table slots of the spatial index (power of two, multiple of 4096)
 // cells of side 2 R_L / 2^fine (grid.h): 1 measured best at 100k (K=3000: 716 -> 648 us, uniform 2361 -> 2138; 2: no further gain)
-static int grid_fine() { static const int f = [] { const int v = obb_dev_switch("OBB_GRID_FINE", 1); return (v < 0 || v > 2) ? 1 : v; }(); return f; }
+constexpr int kGridFine = 1;
 // Skip rules of the quad NMS (piou_device.h): bit 0 = the two exact cone rules (proved), bit 1 = the bounding-box rule (measured noise
 // bound).  OBB_NMS_POLY_STRICT=1: cone rule only (every other pair is clipped); =2: no rule at all, every pair is clipped.
 static int quad_skip() {
   static const int f = [] { const char* e = getenv("OBB_NMS_POLY_STRICT"); const int v = e ? atoi(e) : 0; return v == 1 ? 1 : (v >= 2 ? 0 : 3); }();
   return f;
 }
-static uint32_t grid_slots(int64_t n) { return (n >= 262144 || (grid_fine() > 0 && n >= 32768)) ? 65536u : 16384u; }
+static uint32_t grid_slots(int64_t n) { return n >= 32768 ? 65536u : 16384u; }
 constexpr int64_t kGridMinN = 8192;    // below this the exhaustive cross phase is cheaper than building the index
 
 // One persistent launch runs the whole step loop (nms_core.h).  Grid: one 512-thread workgroup per CU at most --
@@ -639,9 +626,7 @@ static int nms_steps(int kind, NmsArgs& a, const Carve& cv, int64_t nseg, int64_
   if (!(pre & kNmsBarZeroed) && hipMemsetAsync(cv.bar, 0, cv.bar_bytes, st) != hipSuccess) return OBB_ERR_LAUNCH;
   a.bar = cv.bar; a.abort_flag = cv.abort_flag; a.nseg = (int)nseg;
   a.bar_sub = cv.nedges + kMaxTeams;                 // group counters of the grid-wide barrier, behind the per-team words
-  a.cap_first = cap_first();
-  { static const int grow = [] { const int v = obb_dev_switch("OBB_NMS_GROW", 2); return (v < 2 || v > 8) ? 2 : v; }(); a.grow_sparse = grow; }
-  { static const int lpt = obb_dev_switch("OBB_NMS_LPT", 1) & 1; a.lpt = lpt; }      // A/B switch (development builds): rows of a chunk largest first
+  a.cap_first = kCapFirst;
   static const int phase_prof = [] { const char* e = getenv("OBB_NMS_PHASE_PROF"); return (e && atoi(e)) ? 1 : 0; }();
   a.prof = nullptr;
   if (phase_prof && a.resume == nullptr) {   // development aid: print the previous call's phase times (synchronises!)
@@ -840,13 +825,11 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
   const unsigned gb = (unsigned)((n + T - 1) / T);
   int pre = 0;
   // spatial index for the cross phases (grid.h): rotated boxes, one list, conservative rejects allowed (thr >= 0)
-  static const int no_grid = obb_dev_switch("OBB_NMS_NO_GRID", 0) != 0;          // A/B switch (development builds)
-  const bool use_grid = !no_grid && kind == 0 && cv.grid.meta != nullptr && thr >= 0.f && n < (1ll << 24);
-  static const int no_slabs = obb_dev_switch("OBB_NMS_NO_SLABS", 0) != 0;        // A/B switch (development builds)
+  const bool use_grid = kind == 0 && cv.grid.meta != nullptr && thr >= 0.f && n < (1ll << 24);
   // long lists without a limit on the kept boxes: the phase-kernel path (nms_mk.h) -- no index of all boxes, no slab decomposition
   MkFeedback* const fbk = (use_grid && cv.mk_cidx != nullptr && n >= kMkMinN && max_keep <= 0) ? mk_feedback(n) : nullptr;
   const bool use_mk = use_grid && cv.mk_cidx != nullptr && n >= kMkMinN && max_keep <= 0 && mk_choose(fbk);
-  const bool use_slabs = use_grid && !use_mk && !no_slabs && max_keep <= 0;   // (a limit on the kept boxes keeps the call one list: the windows are per list)
+  const bool use_slabs = use_grid && !use_mk && max_keep <= 0;   // (a limit on the kept boxes keeps the call one list: the windows are per list)
   {
     ProfScope ps(PROF_NMS_SORT, st);
     LocalExtras x{};
@@ -879,16 +862,11 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
     // first chunk: 2048, or 4096 when the previous call of the size class kept more than an eighth of its boxes (sparse data: few
     // conflicts inside a chunk, the steps are what costs -- measured at 100k: S-uniform 1.05 -> 0.94 ms, S-clustered K=3000 0.54 -> 0.58).
     // (the edge list holds the worst case of kMkTile = C members; a larger chunk that outgrows it hands over to the persistent kernel)
-    static const int mk_cap_env = [] { const char* e = getenv("OBB_NMS_MK_CHUNK"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : (v > kMkCapMax ? kMkCapMax : v); }();   // (measurement aid)
     const int kept_prev = fbk ? *(volatile int*)(fbk->words + 1) : -1;
-    m.capmax = kMkCapMax; m.cap_first = mk_cap_env >= 64 ? mk_cap_env : ((kept_prev >= 0 && (int64_t)kept_prev * 8 > n) ? 4096 : 2048);
+    m.capmax = kMkCapMax; m.cap_first = (kept_prev >= 0 && (int64_t)kept_prev * 8 > n) ? 4096 : 2048;
     static_assert(kMkTile == 8192, "cap_max(1)");
     m.thr = thr;
     // (OBB_NMS_MK_PEND: a smaller pending list, so that tests reach the overflow hand-over without two million undecided pairs)
-    // The pending pairs go straight to the exact clip: nothing compacts a wave between the interval and the clip there, so a wave
-    // ran the clip unless the interval had decided all 64 of its pairs -- the interval stage was 10-17 us of every call at 100k (K=300
-    // 0.287 -> 0.277 ms, K=3000 0.446 -> 0.433, uniform 0.854 -> 0.837 on one box).  OBB_NMS_MK_NOFULL=0 puts it back (read per call).
-    m.skip_full = [] { const char* e = getenv("OBB_NMS_MK_NOFULL"); return (e && *e == '0') ? 0 : 1; }();
     static const int mk_pend_cap = [] { const char* e = getenv("OBB_NMS_MK_PEND"); const int v = e ? atoi(e) : 0; return (v > 0 && v < kMkPend1) ? v : kMkPend1; }();
     m.pend1 = cv.mk_pend1; m.cap1 = mk_pend_cap; m.num_keep = nullptr;    // (k_finalize below writes the count)
     m.hint_host = fbk ? fbk->words : nullptr;
@@ -911,7 +889,7 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
   NmsArgs a{};
   if (use_grid) {
     a.gmeta = cv.grid.meta; a.bbpart = cv.grid.bbpart; a.nparts = cv.grid.nparts; a.gcnt = cv.grid.cnt; a.gstart = cv.grid.start;
-    a.gsorted = cv.grid.sorted; a.gslot = cv.grid.slot_of; a.gwsum = cv.grid.wsum; a.ulist = cv.grid.ulist; a.gmask = cv.grid.mask; a.gfine = grid_fine();
+    a.gsorted = cv.grid.sorted; a.gslot = cv.grid.slot_of; a.gwsum = cv.grid.wsum; a.ulist = cv.grid.ulist; a.gmask = cv.grid.mask; a.gfine = kGridFine;
   }
   if (use_slabs) {
     a.slab_cover = cv.grid.slab_cover; a.slab_flag = cv.grid.slab_flag; a.slab_cnt = cv.grid.slab_cnt; a.slab_tot = cv.grid.slab_tot; a.slab_keep = cv.grid.slab_keep;
@@ -924,10 +902,9 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
     // Round 6: twice that when the previous call of the size class kept more than an eighth of its boxes (thousands of objects per
     // slab: few conflicts inside a chunk, the steps are what costs) -- S-clustered K=3000 + 18 class offsets (40,000 of 100,000 kept)
     // 0.579 -> 0.506 ms, while K=300 + 18 offsets (6,900 kept) would lose 0.05 ms with it.
-    static const int slab_cap = [] { const int v = obb_dev_switch("OBB_NMS_SLAB_CAP", 0); return v < 0 ? 0 : v; }();
     const int kept_before = fbk ? *(volatile int*)(fbk->words + 1) : -1;
     const int slab_auto = (kept_before >= 0 && (int64_t)kept_before * 8 > n) ? 2048 : 1024;
-    a.slab_cap = ((slab_cap ? slab_cap : slab_auto) + 63) / 64 * 64;
+    a.slab_cap = slab_auto;
   }
   a.rec = cv.rec; a.order = cv.vals_b; a.alive = cv.alive; a.seg_begin = cv.seg_begin; a.seg_end = cv.seg_end;
   a.keep_cnt = cv.keep_cnt; a.keep_out = keep_out;

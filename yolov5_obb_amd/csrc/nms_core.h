@@ -108,8 +108,6 @@ struct NmsArgs {
   int alive2_words, kept_words;
   const SlabPlan* slab_plan;  // written by k_slab_split in front of this launch (NULL: no decomposition was looked for)
   int slab_cap;               // > 0: upper limit of a slab team's chunk capacity
-  int grow_sparse;            // chunk growth factor after a sparse chunk (<= 2: always double)
-  int lpt;                    // 1: the resolver hands the kept rows of a chunk to the indexed cross phase LARGEST FIRST (nms_resolve)
   const NmsResume* resume;    // optional (one list, no slabs): see NmsResume
 };
 
@@ -249,31 +247,14 @@ struct WaveLds {
   float4 align16[0];
 };
 
-// Phases that run once per call or once per step: forceinline by default; a build may turn any of them into a real
-// function (-DOBB_COLD_x="__device__ __attribute__((noinline))") to shorten the live ranges of the persistent kernel.
-#ifndef OBB_COLD_RESOLVE
-#define OBB_COLD_RESOLVE __device__ __forceinline__
-#endif
-#ifndef OBB_COLD_GRID
-#define OBB_COLD_GRID __device__ __forceinline__
-#endif
-#ifndef OBB_COLD_SLAB
-#define OBB_COLD_SLAB __device__ __forceinline__
-#endif
-#ifndef OBB_COLD_SELECT
-#define OBB_COLD_SELECT __device__ __forceinline__
-#endif
-#ifndef OBB_STAGE_ATTR
-#define OBB_STAGE_ATTR __attribute__((noinline))
-#endif
 // The two expensive decision stages are real functions (one body per geometry): the pair phase and the forms of the
 // cross phase all drain their queues through them.
 template <class G, class TH>
-__device__ OBB_STAGE_ATTR int nms_stage_full(const float4* ra, const float4* rb, TH thr) {
+__device__ __attribute__((noinline)) int nms_stage_full(const float4* ra, const float4* rb, TH thr) {
   return G::classify_full(ra, rb, thr);
 }
 template <class G, class TH>
-__device__ OBB_STAGE_ATTR bool nms_stage_exact(const float4* ra, const float4* rb, TH thr, float* scr) {
+__device__ __attribute__((noinline)) bool nms_stage_exact(const float4* ra, const float4* rb, TH thr, float* scr) {
   return G::hit_exact(ra, rb, thr, scr);
 }
 
@@ -296,7 +277,7 @@ __device__ __forceinline__ bool stage_exact(const float4* ra, const float4* rb, 
 // pair (geom.h: hit_exact_coop) -- a leftover drain of a dozen quad pairs costs three term times instead of sixteen.
 template <class G> struct has_coop { template <class T> static constexpr bool f(decltype(T::HAS_COOP)*) { return T::HAS_COOP; } template <class T> static constexpr bool f(...) { return false; } static constexpr bool value = f<G>(nullptr); };
 template <class G, class TH>
-__device__ OBB_STAGE_ATTR bool nms_stage_exact_coop(bool want, const float4* ra, const float4* rb, TH thr, float* scr_wave) {
+__device__ __attribute__((noinline)) bool nms_stage_exact_coop(bool want, const float4* ra, const float4* rb, TH thr, float* scr_wave) {
   if constexpr (has_coop<G>::value) return G::hit_exact_coop(want, ra, rb, thr, scr_wave);
   else return false;
 }
@@ -334,7 +315,7 @@ struct PairQueue {
 // chunk = the first `cap` alive positions in [cur, se); their positions go to this workgroup's LDS list; returns the
 // chunk size and moves `cur` behind the last member.  Members keep their alive bit: nothing reads positions below
 // the cursor again.
-OBB_COLD_SELECT int nms_select(const NmsArgs& a, int se, int& cur, int cap, uint32_t* cidx, int* s_i) {
+__device__ __forceinline__ int nms_select(const NmsArgs& a, int se, int& cur, int cap, uint32_t* cidx, int* s_i) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int w_first = cur >> 6, w_last = (se - 1) >> 6;
   int off = 0;
@@ -643,11 +624,14 @@ __device__ __forceinline__ void nms_pairs(const NmsArgs& a, int tm, int cn, cons
 // its kill, so the rounds get cheaper geometrically.  A list too long for LDS is streamed read-only from global memory
 // for the first rounds, until what is left of it fits.
 // LDS (aliasing the wave scratch): state[capmax] | blocked[capmax] | edges[...]
+// Contract: a workgroup of exactly kNmsThreads threads runs it (the loops stride by kNmsThreads), and smem_bytes >= 6 * capmax
+// (state + blocked + the ordered output list of one chunk, 4 bytes per member, which reuses the edge area).  launch_persist checks
+// the bound at run time, the phase kernels (nms_mk.h: mk_resolve_phase) at compile time.
 // returns the number of kept boxes of the chunk (also published in nrows[g])
 // hasin (optional, [cn] bytes, nms_mk.h): != 0 where at least one edge points AT the member, set while the edges were written.  The
 // members nobody points at are kept before the first round instead of after it: the first pass over the list already kills and prunes.
-OBB_COLD_RESOLVE int nms_resolve(const NmsArgs& a, int g, int sb, int tm, int cn, int kept_before, const uint32_t* cidx, uint8_t* smem,
-                           size_t smem_bytes, int* s_i, const uint8_t* hasin = nullptr) {
+__device__ __forceinline__ int nms_resolve(const NmsArgs& a, int g, int sb, int tm, int cn, int kept_before, const uint32_t* cidx, uint8_t* smem,
+                                           size_t smem_bytes, int* s_i, const uint8_t* hasin = nullptr) {
   const int tid = threadIdx.x;
   uint8_t* state = smem;              // 0 undecided, 1 kept, 2 dead
   uint8_t* blocked = smem + a.capmax;
@@ -875,7 +859,8 @@ OBB_COLD_RESOLVE int nms_resolve(const NmsArgs& a, int g, int sb, int tm, int cn
   // idempotent), the output order comes from `olist`.  Four buckets by radius relative to the chunk's largest, in bucket order.
   uint32_t* lcode = olist + a.capmax;                         // [total] bucket << 16 | slot in the bucket   (lcap >= 3 capmax + 8: checked below)
   int* lcnt = reinterpret_cast<int*>(olist + 3 * (size_t)a.capmax);   // [0..3] bucket sizes, [4] largest radius (float bits; radii are >= 0)
-  const bool lpt = (a.lpt & 1) != 0 && a.gmeta != nullptr && a.nseg == 1 && a.keep_out != nullptr && total >= 512 && lcap >= 3LL * a.capmax + 8;
+  // (gmeta == NULL -- no spatial index, as in the phase kernels' resolve (nms_mk.h: mk_resolve_phase) -- keeps score order)
+  const bool lpt = a.gmeta != nullptr && a.nseg == 1 && a.keep_out != nullptr && total >= 512 && lcap >= 3LL * a.capmax + 8;
   if (lpt) {
     if (tid < 5) lcnt[tid] = 0;
     __syncthreads();
@@ -1220,10 +1205,7 @@ __device__ __forceinline__ void nms_cross(const NmsArgs& a, const uint32_t* rows
   }
 }
 
-#ifndef OBB_SCAN_BATCH
-#define OBB_SCAN_BATCH 4
-#endif
-constexpr int kScanBatch = OBB_SCAN_BATCH;          // blocks of candidates in flight per wave
+constexpr int kScanBatch = 4;          // blocks of candidates in flight per wave
 // Indexed form (grid.h): a kept row only needs the boxes of the cells around it.  The boxes of the call sit once more in
 // CELL order (built inside the kernel: count, scan, scatter); a query window is a few cell rows per level, and the boxes of
 // one cell row are ONE contiguous range of that array (the slot hash is linear in cx), read coalesced by the 64 lanes
@@ -1467,14 +1449,7 @@ __device__ __forceinline__ void nms_cross_grid(const NmsArgs& a, const GridPlan&
               val[u] = lane < (int)(be[u] & 127u);
               cq[u] = make_float4(0.f, 0.f, 0.f, 0.f);
               if (val[u]) {
-#ifdef OBB_GRID_COHERENT_LOADS
-                const u64* src = reinterpret_cast<const u64*>(a.gsorted + (size_t)(be[u] >> 7) + lane);
-                const u64 lo = ldg_agent(src), hi = ldg_agent(src + 1);
-                cq[u] = make_float4(__uint_as_float((uint32_t)lo), __uint_as_float((uint32_t)(lo >> 32)), __uint_as_float((uint32_t)hi),
-                                    __uint_as_float((uint32_t)(hi >> 32)));
-#else
                 cq[u] = a.gsorted[(size_t)(be[u] >> 7) + lane];
-#endif
               }
             }
             // circle test + the entry's dead flag (set by whoever killed the box, see `kill`): most candidates of a later
@@ -1531,7 +1506,7 @@ constexpr int kGridMinRows = 512;
 // (guideline 16).  The slot counters are back to zero when the scatter is done.
 // Returns 0: built; 1: barrier abort; 2: not worth using (no usable extent, or more than 1/16 of the boxes are brute).
 template <class G>
-OBB_COLD_GRID int grid_build(const NmsArgs& a, const GridPlan& gp, int c0, int wg, int T, TeamBar& bar, int* s_flag, int* s_i,
+__device__ __forceinline__ int grid_build(const NmsArgs& a, const GridPlan& gp, int c0, int wg, int T, TeamBar& bar, int* s_flag, int* s_i,
                                           uint32_t& level_mask, int& n_brute) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int M = (int)a.gmask + 1;
@@ -1800,7 +1775,7 @@ __device__ __forceinline__ int slab_setup(const NmsArgs& a, float bin_x0, float 
       while (fits(est + 64)) est += 64;
       c = (int)est;
     }
-    if (a.slab_cap > 0 && c > a.slab_cap) c = a.slab_cap;      // (OBB_NMS_SLAB_CAP: measurements)
+    if (a.slab_cap > 0 && c > a.slab_cap) c = a.slab_cap;
     misc[1] = (mx <= kSlabMaxSeg && nonempty >= 2 && nonempty <= NB && c >= 512) ? 1 : 0;
     misc[2] = nonempty; misc[3] = c;
     if (wg == 0) { SL.cap = c; SL.ecap = (long long)c * (c - 1) / 2; }
@@ -1960,7 +1935,7 @@ __global__ __launch_bounds__(kNmsThreads) void k_slab_split(NmsArgs a, SlabPlan*
 // After every team has finished its slab (and one more barrier of the whole grid): the kept boxes are the set bits of a
 // bitmap over the ORIGINAL sorted positions; position order is score order, so the output is an ordered compaction of
 // that bitmap.  Every workgroup scans all words for the ranks (n / 64 words: 1563 at N = 100k) and emits its share.
-OBB_COLD_SLAB void slab_merge(const u64* kept_bits, int n, const uint32_t* order, int64_t* keep_out, int* keep_cnt, int* s_i) {
+__device__ __forceinline__ void slab_merge(const u64* kept_bits, int n, const uint32_t* order, int64_t* keep_out, int* keep_cnt, int* s_i) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int NB = gridDim.x, wg = blockIdx.x;
   const int W = (n + 63) >> 6;
@@ -2214,9 +2189,7 @@ __global__ __launch_bounds__(kNmsThreads) __attribute__((amdgpu_waves_per_eu(1, 
       if (prof) a.prof[6] += 1;
       // (measured: jumping to the largest chunk when most of a chunk is kept -- sparse data -- is slower, 0.78 -> 0.96 ms at
       //  100k with 18 class offsets: the pair phase grows with the square of the chunk)
-      // (a.grow_sparse > 2: a chunk that kept more than half of its boxes -- sparse data -- is followed by one that many times
-      //  larger instead of twice; OBB_NMS_GROW, measurements)
-      if (cap < a.capmax) { cap *= (a.grow_sparse > 2 && 2 * nr > cn) ? a.grow_sparse : 2; if (cap > a.capmax) cap = a.capmax; }
+      if (cap < a.capmax) { cap *= 2; if (cap > a.capmax) cap = a.capmax; }
     }
   }
   if constexpr (G::HAS_GRID && GRID) {

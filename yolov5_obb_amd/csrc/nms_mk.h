@@ -81,7 +81,6 @@ struct MkArgs {
   int64_t* num_keep;                      // written by whoever completes the call
   const int* bbpart; int nparts;
   int capmax, cap_first;
-  int skip_full;                          // decide kernels: 1 = every open pending pair goes straight to the exact clip (see mk_decide_phase)
   float thr;
   uint4* pend1; int cap1;                 // {query position, entry position, entry index << 16 | query index (pairs), -} the quick tests left undecided
   int* hint_host;                         // pinned words: [0] steps the call needed, [1] boxes it kept (read by the NEXT call of this thread; may be NULL)
@@ -857,10 +856,12 @@ __device__ void mk_cross_lds_phase(const MkArgs& a, MkLdsCross& S, int wg, int n
   }
 }
 
-// ------------------------------------------------------------------ the interval and the exact clip on the pending list (dense: one lane per pair)
+// ------------------------------------------------------------------ the exact clip on the pending list (dense: one lane per pair)
 // The list is short against the machine (at most a trip or two per wave), so what counts is the length of a wave's dependent
-// chain: the pair's positions come with the entry (no look-up), and the lanes the interval leaves undecided run the exact clip
-// right there on the records they already hold instead of queueing for a full wave.
+// chain: the pair's positions come with the entry (no look-up), and every open pair runs the exact clip right there on the
+// records it already holds.  (An IoU-interval stage in front of the clip was measured and not kept: nothing compacts a wave
+// between the two, so a wave ran the clip unless the interval had decided all 64 of its pairs -- the interval stage was
+// 10-17 us of every call at 100k: K=300 0.287 -> 0.277 ms, K=3000 0.446 -> 0.433, uniform 0.854 -> 0.837 on one box.)
 template <bool CROSS>
 __device__ __forceinline__ void mk_decide_phase(const MkArgs& a, float* scr_wave) {
   MkCtl* c = a.ctl;
@@ -871,24 +872,25 @@ __device__ __forceinline__ void mk_decide_phase(const MkArgs& a, float* scr_wave
   const int gw = (int)((threadIdx.x >> 6) * gridDim.x + blockIdx.x), nw = (int)((gridDim.x * blockDim.x) >> 6);
   for (int base = gw * 64; base < n1; base += nw * 64) {
     const int i = base + lane;
-    int res = 0; uint4 p = make_uint4(0u, 0u, 0u, 0u);
+    bool open = false; uint4 p = make_uint4(0u, 0u, 0u, 0u);
     const float4 *ra = a.rec, *rb = a.rec;
     if (i < n1) {
       p = a.pend1[i];
       ra = a.rec + (size_t)p.y * 4; rb = a.rec + (size_t)p.x * 4;          // (the entry = the earlier box first)
       // (cross: a query that another row has removed meanwhile -- most have a quick hit from the row of their own object -- needs
       //  no further decision)
-      bool open = true;
+      open = true;
       if constexpr (CROSS) open = (ldg_agent(a.alive + (p.z >> 6)) >> (p.z & 63)) & 1ull;
-      if (open) res = a.skip_full ? 2 : RotGeom::classify_full(ra, rb, a.thr);
     }
-    bool h = res == 1;
-    if (__ballot(res == 2)) {
-      if (res == 2) h = RotGeom::hit_exact(ra, rb, a.thr, scr_wave + lane);
+    bool h = false;
+    if (__ballot(open)) {
+      if (open) h = RotGeom::hit_exact(ra, rb, a.thr, scr_wave + lane);
     }
     mk_hit<CROSS>(a, h, p.z);
   }
 }
+
+constexpr size_t kMkSerialLds = 128 * 1024;   // dynamic LDS of the kernels that run a serial phase (resolve: the edge list in LDS)
 
 // ------------------------------------------------------------------ C: resolve the chunk, append its kept boxes to the output, publish the kept bits (ONE workgroup)
 __device__ void mk_resolve_phase(const MkArgs& a, uint8_t* smem, size_t smem_bytes, int* s_i, u64* t0) {
@@ -898,7 +900,10 @@ __device__ void mk_resolve_phase(const MkArgs& a, uint8_t* smem, size_t smem_byt
   const int E = ldg_agent(a.nedges);
   NmsArgs r{};
   r.rec = a.rec; r.order = a.order; r.keep_cnt = a.keep_cnt; r.keep_out = a.keep_out; r.rows = a.rows; r.nrows = a.nrows;
-  r.edges = a.edges; r.nedges = a.nedges; r.ecap = a.ecap; r.n = a.n; r.nseg = 1; r.capmax = a.capmax; r.max_keep = 0; r.lpt = 0; r.prof = a.prof;
+  r.edges = a.edges; r.nedges = a.nedges; r.ecap = a.ecap; r.n = a.n; r.nseg = 1; r.capmax = a.capmax; r.max_keep = 0; r.prof = a.prof;
+  // (r.gmeta stays NULL: nms_resolve keeps the kept rows in score order -- no largest-first ordering for the cross probe)
+  static_assert(kMkThreads == kNmsThreads, "nms_resolve runs on a workgroup of kNmsThreads threads");
+  static_assert(kMkSerialLds >= 6 * (size_t)kMkCapMax, "nms_resolve needs 6 bytes of LDS per member of a kMkCapMax chunk");
   __syncthreads();
   const int total = nms_resolve(r, 0, 0, 0, cn, kept_before, a.cidx, smem, smem_bytes, s_i, a.hasin);
   // the kept bits of the chunk members for the cross probe (nms_resolve leaves the members' states at the head of its LDS block)
@@ -926,8 +931,6 @@ __device__ void mk_resolve_phase(const MkArgs& a, uint8_t* smem, size_t smem_byt
     if (last) mk_finish(a, c, kept_before + total, step + 1);
   }
 }
-
-constexpr size_t kMkSerialLds = 128 * 1024;   // dynamic LDS of the kernels that run a serial phase (resolve: the edge list in LDS)
 
 // Every kernel of a step first looks at the control block: the call may be complete (done), the phase kernels may have stood back
 // (bail: the persistent kernel behind them carries on), or the step's turn may not have come (stage).

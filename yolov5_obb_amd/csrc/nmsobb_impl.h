@@ -451,13 +451,11 @@ __global__ __launch_bounds__(256) void k_tiny_cross(const float4* __restrict__ c
 }
 
 // per image: sort range, number of positions that take part, mode:
-//   0  single list (the reference's formulation)
+//   0  single list (the reference's formulation) -- also every image with more than max_nms candidates (the top max_nms by
+//      confidence must be cut first, :845-846)
 //   1  one NMS segment per class, class in the top key byte (k_rekey) -- needs <= max_nms candidates
-//   2  more than max_nms candidates: single-list sort first (the top max_nms by confidence must be cut, :845-846), then one
-//      stable pass groups the survivors by class (seg_group_by_class); segments per class as in mode 1
 __global__ void k_cand_segments(const int* __restrict__ cnt, const int* __restrict__ tiny, int bs, long long cap_img, long long max_nms,
-                                int class_ok, int group_ok, int* sort_begin, int* sort_end, int* img_end, int* mode, int* grp_begin,
-                                int* grp_end) {
+                                int class_ok, int* sort_begin, int* sort_end, int* img_end, int* mode) {
   int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= bs) return;
   long long c = cnt[g * kCntPad];
@@ -468,9 +466,7 @@ __global__ void k_cand_segments(const int* __restrict__ cnt, const int* __restri
   const bool over_nms = max_nms > 0 && c > max_nms;
   if (over_nms) c = max_nms;                                 // :845-846 top max_nms by confidence
   img_end[g] = b0 + (int)c;
-  const int m = (class_ok && !over_cap && !img_single_list(tiny[g])) ? (over_nms ? (group_ok ? 2 : 0) : 1) : 0;   // group_ok: the host launches the pass
-  mode[g] = m;
-  grp_begin[g] = b0; grp_end[g] = (m == 2) ? b0 + (int)c : b0;      // range of the class-grouping pass (empty unless mode 2)
+  mode[g] = (class_ok && !over_cap && !img_single_list(tiny[g]) && !over_nms) ? 1 : 0;
 }
 
 // class-segmented images: key (score_desc << 32 | anchor*nc + cls)  ->  (cls << 56 | score_desc << 24 | anchor)
@@ -499,8 +495,8 @@ __device__ __forceinline__ int key_lower_bound_range(const unsigned long long* k
 
 // segment table: ncs segments per image (ncs = nc, or 1 when the call is class-agnostic)
 __global__ void k_class_bounds(const unsigned long long* __restrict__ keys_sorted, const int* __restrict__ sort_begin,
-                               const int* __restrict__ img_end, const int* __restrict__ mode, const uint32_t* __restrict__ digit_base,
-                               int bs, int ncs, int* __restrict__ seg_begin, int* __restrict__ seg_end, int* __restrict__ keep_cnt) {
+                               const int* __restrict__ img_end, const int* __restrict__ mode, int bs, int ncs, int* __restrict__ seg_begin,
+                               int* __restrict__ seg_end, int* __restrict__ keep_cnt) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= bs * ncs) return;
   const int g = s / ncs, c = s - g * ncs;
@@ -509,23 +505,10 @@ __global__ void k_class_bounds(const unsigned long long* __restrict__ keys_sorte
   if (mode[g] == 1) {
     lo = key_lower_bound_range(keys_sorted, b0, e0, (unsigned long long)c << 56);
     hi = (c >= 255) ? e0 : key_lower_bound_range(keys_sorted, b0, e0, (unsigned long long)(c + 1) << 56);
-  } else if (mode[g] == 2) {                                   // class runs of the grouping pass
-    lo = b0 + (int)digit_base[(size_t)g * 256 + c];
-    hi = (c + 1 < ncs && c + 1 < 256) ? b0 + (int)digit_base[(size_t)g * 256 + c + 1] : e0;
   } else if (c == 0) {
     hi = e0;                                                   // single list: everything in segment 0 of the image
   }
   seg_begin[s] = lo; seg_end[s] = hi; keep_cnt[s] = 0;
-}
-
-// mode-2 images: the grouped range comes back from the ping buffers
-__global__ void k_copy_grouped(const unsigned long long* __restrict__ ksrc, unsigned long long* __restrict__ kdst,
-                               const uint32_t* __restrict__ vsrc, uint32_t* __restrict__ vdst, const int* __restrict__ grp_begin,
-                               const int* __restrict__ grp_end) {
-  const int g = blockIdx.y;
-  const int p = grp_begin[g] + blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= grp_end[g]) return;
-  kdst[p] = ksrc[p]; vdst[p] = vsrc[p];
 }
 
 __global__ void k_prep_cand(const float4* __restrict__ cand, const uint32_t* __restrict__ vals_sorted,
@@ -587,7 +570,7 @@ __global__ __launch_bounds__(1024) void k_sort_prep_lds(const float4* __restrict
                                                         uint32_t* __restrict__ vals_out, const int* __restrict__ cnt,
                                                         const int* __restrict__ tiny, int bs, long long cap_img, long long max_nms,
                                                         int class_ok, long long A, int nc, int ncs, float class_offset, int* sort_begin,
-                                                        int* sort_end, int* img_end, int* mode, int* grp_begin, int* grp_end,
+                                                        int* sort_end, int* img_end, int* mode,
                                                         int* __restrict__ seg_begin, int* __restrict__ seg_end, int* __restrict__ keep_cnt,
                                                         float4* __restrict__ rec, u64* __restrict__ alive, int* __restrict__ ticket,
                                                         int plan_nb, int plan_chunk, int4* __restrict__ plan, int* __restrict__ seg_size, int P,
@@ -635,7 +618,6 @@ __global__ __launch_bounds__(1024) void k_sort_prep_lds(const float4* __restrict
   if (q > 0 && m != 1) return;                                 // one list per image: part 0 does it all
   if (tid == 0 && q == 0) {
     sort_begin[g] = b0; sort_end[g] = b0 + n; img_end[g] = b0 + e; mode[g] = m;
-    grp_begin[g] = b0; grp_end[g] = b0;
   }
   if (tid < 256) s_hist[tid] = 0;
   if (tid < kSortLdsMax / 2 / 64) s_abits[tid] = 0ull;
@@ -968,8 +950,7 @@ __global__ __launch_bounds__(256) void k_gather_out(const float4* __restrict__ c
   const long long row0 = packed ? s_rows[0] + s_rows[1] + s_rows[2] + s_rows[3] : (long long)g * max_det;
   const int md = mode[g];
   const bool single = md == 0;
-  // merge key of entry e = (class c, index k): the mode-1 key rotated so that it orders by (score, anchor, class);
-  // mode 2 keeps the single-list key (score, anchor*nc + class), which already is the global order
+  // merge key of entry e = (class c, index k): the mode-1 key rotated so that it orders by (score, anchor, class)
   auto entry_pos = [&](int c, int k) -> uint32_t { return (uint32_t)keep[(size_t)s_seg[c] + k]; };
   auto mkey_at = [&](uint32_t p) -> unsigned long long {
     const unsigned long long k = keys_sorted[p];
@@ -1023,17 +1004,8 @@ __global__ __launch_bounds__(256) void k_gather_out(const float4* __restrict__ c
 // order, same records as the sort kernel's (k_sort_prep_lds: "by_class"); an image that keeps ONE list (img_single_list, more than
 // max_nms candidates) is segment 0's if it fits.  What does not fit a segment raises too_big like a segment of the sort's: the caller
 // repeats the call on the persistent kernel.
-// (compile-time switches of the front end, measured within 1 us of each other on the bs16 step: keys per thread and trip, the first
-//  trip requested together with the image's counter, the rank count with eight reads in flight)
-#ifndef OBB_SELF_KPT
-#define OBB_SELF_KPT 8
-#endif
-#ifndef OBB_SELF_SPEC
-#define OBB_SELF_SPEC 1
-#endif
-#ifndef OBB_SELF_RU
-#define OBB_SELF_RU 1
-#endif
+// (the front end's alternatives -- fewer keys per thread and trip, the first trip requested after the image's counter, the rank
+//  count one read at a time -- were measured within 1 us of this form on the bs16 step and not kept)
 struct SmallSelfSort {
   static constexpr bool kSelf = true;
   // an image's candidate count, its top-max_nms cut and its mode exactly as k_sort_prep_lds decides them (class_ok holds: the
@@ -1053,11 +1025,11 @@ struct SmallSelfSort {
                                                        uint32_t* s_pv, int* s_n) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int g = seg / a.ncs, c = seg - g * a.ncs;
-    constexpr int KPT = OBB_SELF_KPT;                            // keys per thread and trip
+    constexpr int KPT = 8;                                       // keys per thread and trip
     const size_t b0 = (size_t)g * (size_t)a.cap_img;
     // the first trip's keys are requested TOGETHER with the image's counter (slots behind the count hold stale keys of the
     // workspace: read, never used) -- one round trip less in front of every segment
-    const int spec = !OBB_SELF_SPEC ? 0 : (a.cap_img < (long long)KPT * kSmallThreads ? (int)a.cap_img : KPT * kSmallThreads);
+    const int spec = a.cap_img < (long long)KPT * kSmallThreads ? (int)a.cap_img : KPT * kSmallThreads;
     unsigned long long k[KPT];
 #pragma unroll
     for (int u = 0; u < KPT; u++) { const int i = u * kSmallThreads + tid; k[u] = i < spec ? a.keys_in[b0 + i] : 0ull; }
@@ -1072,7 +1044,7 @@ struct SmallSelfSort {
     __syncthreads();
     const uint32_t nc = (uint32_t)a.nc, lim = (uint32_t)((unsigned long long)a.A * nc);   // (A * nc + label rows < 2^32: checked by the launcher)
     for (int i0 = 0; i0 < n; i0 += KPT * kSmallThreads) {        // (workgroup-uniform trip count: ballots inside)
-      if (i0 > 0 || !OBB_SELF_SPEC) {
+      if (i0 > 0) {
 #pragma unroll
         for (int u = 0; u < KPT; u++) { const int i = i0 + u * kSmallThreads + tid; k[u] = i < n ? a.keys_in[b0 + i] : 0ull; }
       }
@@ -1114,7 +1086,7 @@ struct SmallSelfSort {
       const float4 c0 = a.cand[ci * 2], c1 = a.cand[ci * 2 + 1]; // under way during the count
       int rank = 0, j = 0;
       const ulonglong2* p2 = reinterpret_cast<const ulonglong2*>(st_key);
-      for (; OBB_SELF_RU && j + 16 <= nm; j += 16) {                            // eight 16-byte broadcast reads in flight (one at a time: 64 cycles each)
+      for (; j + 16 <= nm; j += 16) {                                           // eight 16-byte broadcast reads in flight (one at a time: 64 cycles each)
         ulonglong2 v[8];
 #pragma unroll
         for (int z = 0; z < 8; z++) v[z] = p2[(j >> 1) + z];
@@ -1377,8 +1349,9 @@ static inline size_t obb_state_bytes(int64_t bs) { return align_up((size_t)bs * 
 
 struct ObbCarve {
   float4* cand; unsigned long long *keys_a, *keys_b; uint32_t *vals_a, *vals_b; int* cnt; int *sort_begin, *sort_end;
-  int *img_end, *mode, *tiny, *grp_begin, *grp_end, *ticket;
-  uint32_t *srs_hist, *digit_base;
+  int *img_end, *mode, *tiny, *ticket;
+  uint32_t* srs_hist;
+  int* seg_size;      // [bs][256] segment sizes for the planner of the in-LDS sort path
   int64_t* keep;
   Carve nms;          // rec/dead/segment state reuse the NMS carve (keys/vals/sort_tmp of it unused)
   void* nms_base;
@@ -1397,9 +1370,8 @@ static int obb_carve(void* base, int64_t bs, int64_t cap_img, int64_t ncs, ObbCa
   cv->vals_a = (uint32_t*)take(n * 4); cv->vals_b = (uint32_t*)take(n * 4);
   cv->cnt = (int*)take(bs * 4 * kCntPad); cv->sort_begin = (int*)take(bs * 4); cv->sort_end = (int*)take(bs * 4);
   cv->img_end = (int*)take(bs * 4); cv->mode = (int*)take(bs * 4); cv->tiny = (int*)take(bs * 4);
-  cv->grp_begin = (int*)take(bs * 4); cv->grp_end = (int*)take(bs * 4);
   cv->ticket = (int*)take(64 + (size_t)(bs + 1) * 4);         // 16 words + k_nms_small's output stage: [bs] + [1]
-  cv->digit_base = (uint32_t*)take((size_t)bs * 256 * 4);
+  cv->seg_size = (int*)take((size_t)bs * 256 * 4);
   cv->srs_hist = (uint32_t*)take((size_t)bs * ((size_t)(cap_img + kSrsTile - 1) / kSrsTile) * 256 * 4);
   cv->keep = (int64_t*)take(n * 8);
   // NMS state sized for bs * cap_img positions
@@ -1429,14 +1401,8 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   cap_img = round_cap(cap_img);
   const int ncs = agnostic ? 1 : nc;                               // NMS segments per image
   // class segmentation needs the class in 8 and the anchor index in 24 key bits
-  static const int no_class_seg = obb_dev_switch("OBB_NO_CLASS_SEG", 0) != 0;    // A/B switch (development builds)
   // (iou_thres < 0: IoU = 0 > thr, boxes of different classes DO suppress each other in the reference's single list)
-  const int class_ok = (!no_class_seg && !agnostic && nc > 1 && A + n_extra < (1ll << 24) && iou_thres >= 0.f && max_wh > 0.f) ? 1 : 0;
-  // the class-grouping pass for images with more than max_nms candidates is only worth launching when such images are expected
-  // (off by default: per-class segments cannot share the max_det early stop of the single list, which usually ends the
-  //  NMS of such images after the first ~2000 of 30000 candidates; OBB_NMS_GROUP_AFTER_CUT=1 enables it)
-  static const int group_cut = obb_dev_switch("OBB_NMS_GROUP_AFTER_CUT", 0) != 0;
-  const int group_ok = (group_cut && class_ok && max_nms > 0 && expected_cand > max_nms) ? 1 : 0;
+  const int class_ok = (!agnostic && nc > 1 && A + n_extra < (1ll << 24) && iou_thres >= 0.f && max_wh > 0.f) ? 1 : 0;
   ObbCarve cv;
   int rc = obb_carve(ws, bs, cap_img, ncs, &cv);
   if (rc) return rc;
@@ -1461,8 +1427,7 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   d.cap_img = cap_img; d.cand = cv.cand; d.keys = cv.keys_a; d.vals = cv.vals_a; d.cnt = cv.cnt; d.tiny = cv.tiny;
   d.win_lo = -0.35f * max_wh; d.win_hi = 0.6f * max_wh;            // 0.95 max_wh wide: circles of different classes cannot touch
 
-  static const int no_lds_sort = obb_dev_switch("OBB_NO_LDS_SORT", 0) != 0;      // A/B switch (development builds)
-  const bool lds_sort = !no_lds_sort && expected_cand > 0 && expected_cand <= kSortLdsHint && !group_ok;
+  const bool lds_sort = expected_cand > 0 && expected_cand <= kSortLdsHint;
   d.z_ticket = nullptr; d.n_ticket = 0; d.z_bar16 = nullptr; d.n_bar16 = 0; d.z_alive16 = nullptr; d.n_alive16 = 0;
   {
     Carve& nv0 = cv.nms;
@@ -1494,22 +1459,21 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   const int64_t max_seg = (max_nms > 0 && max_nms < cap_img) ? max_nms : cap_img;
   // grid of the NMS launch (needed by the planner inside the fused kernel)
   const int nms_capmax = cap_max(bs * ncs);
-  const int plan_chunk = cap_first() < nms_capmax ? cap_first() : nms_capmax;
+  const int plan_chunk = kCapFirst < nms_capmax ? kCapFirst : nms_capmax;
   // Which NMS kernel: one workgroup per segment, everything in LDS (nms_small.h), when the previous call's largest segment fits it
   // (class segments, the in-LDS sort, thr >= 0: its first decision stage uses the conservative bounds); else the persistent kernel.
   const bool small_nms = lds_sort && class_ok && seg_hint > 0 && seg_hint <= kSmallMax && iou_thres >= 0.f && bs * ncs <= 65535;
-  const int plan_nb = (bs * ncs > 1 && !small_nms) ? nms_grid(bs * ncs, bs * max_seg, cap_first()) : 0;
+  const int plan_nb = (bs * ncs > 1 && !small_nms) ? nms_grid(bs * ncs, bs * max_seg, kCapFirst) : 0;
   // k_nms_small's helper workgroups (nms_small.h: a large segment is shared by several workgroups).  A workgroup takes a whole CU
   // (160 KB of LDS), so helpers only run at once with the segments' own workgroups on the CUs the segments leave free: as many as
   // that, none for the bs16 x 16-class step whose 256 segments fill the device (measured there with 256 helpers: 0.121 -> 0.132 ms,
   // the helpers start when the first small segments are through).  Their lists and the parts' bit matrices live in the persistent
   // kernel's edge lists, which this path does not use.  OBB_NMS_SMALL_HELPERS = n pins the number (0: every segment stays whole).
   const int helpers_env = [] { const char* e = getenv("OBB_NMS_SMALL_HELPERS"); const int v = (e && *e) ? atoi(e) : -1; return v > kSmallHelpMax ? kSmallHelpMax : v; }();   // (read per call: tests switch in one process)
-  static const int no_fused_out = obb_dev_switch("OBB_NO_FUSED_OUT", 0) != 0;    // A/B switch (development builds)
   // OBB_NMS_SELF_SORT (read per call): 0 = always the sort kernel, 1 = self-sorting segments where no helpers would run, 2 = default:
   // self-sorting segments wherever they are possible (no helpers then: the sort kernel is what hands them out)
   const int self_env = [] { const char* e = getenv("OBB_NMS_SELF_SORT"); return (e && *e >= '0' && *e <= '2') ? *e - '0' : 2; }();
-  const bool self_possible = small_nms && !out_packed && !no_fused_out && (int64_t)ncs * kSmallMax <= cap_img && self_env != 0;
+  const bool self_possible = small_nms && !out_packed && (int64_t)ncs * kSmallMax <= cap_img && self_env != 0;
   int helpers = 0;
   if (small_nms && !(self_possible && self_env == 2 && helpers_env < 0)) {
     const int64_t free_cus = (int64_t)hw_cu_count() - bs * ncs;
@@ -1547,15 +1511,15 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
     const int parts = (class_ok && ncs >= 8) ? 4 : 1;           // class-segment images: four workgroups each take every fourth class
     k_sort_prep_lds<<<(unsigned)(bs * parts) + (plan_nb > 0 ? 1u : 0u), 1024, lds, st>>>(cv.cand, cv.keys_a, cv.vals_a, cv.keys_b, cv.vals_b, cv.cnt, cv.tiny, (int)bs, cap_img,
                                                    max_nms, class_ok, A, nc, ncs, agnostic ? 0.f : max_wh, cv.sort_begin, cv.sort_end,
-                                                   cv.img_end, cv.mode, cv.grp_begin, cv.grp_end, nv.seg_begin, nv.seg_end, nv.keep_cnt,
+                                                   cv.img_end, cv.mode, nv.seg_begin, nv.seg_end, nv.keep_cnt,
                                                    nv.rec, nv.alive, cv.ticket, plan_nb, plan_chunk, plan_nb > 0 ? nv.plan : nullptr,
-                                                   reinterpret_cast<int*>(cv.digit_base), parts,   // (digit_base: the class-bounds table of the other sort paths, free here)
+                                                   cv.seg_size, parts,
                                                    helpers, help_work, seg_np, seg_ticket);
   } else {
    {
     ProfScope ps(PROF_SEGSORT, st);
-    k_cand_segments<<<gs, 256, 0, st>>>(cv.cnt, cv.tiny, (int)bs, cap_img, max_nms, class_ok, group_ok, cv.sort_begin, cv.sort_end,
-                                        cv.img_end, cv.mode, cv.grp_begin, cv.grp_end);
+    k_cand_segments<<<gs, 256, 0, st>>>(cv.cnt, cv.tiny, (int)bs, cap_img, max_nms, class_ok, cv.sort_begin, cv.sort_end, cv.img_end,
+                                        cv.mode);
     if (class_ok) {
       dim3 gr((unsigned)((cap_img + 255) / 256), (unsigned)bs);
       k_rekey<<<gr, 256, 0, st>>>(cv.cand, cv.keys_a, cv.sort_begin, cv.sort_end, cv.mode, A, nc);
@@ -1570,7 +1534,7 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
       unsigned mask = 0xF0u;                                            // single-list key: score in bytes 4..7
       for (int d = 0; d < 4; d++) if (tb > d * 8) mask |= 1u << d;
       if (class_ok) mask = 0xFFu;                                       // + class-mode key: anchor 0..2, score 3..6, class 7
-      if (bs == 1 && !group_ok && cap_img <= kPsMaxN && nv.sort_tmp_bytes >= ps_scratch_bytes()) {
+      if (bs == 1 && cap_img <= kPsMaxN && nv.sort_tmp_bytes >= ps_scratch_bytes()) {
         PsBuf b{};
         b.run_k = cv.keys_a; b.run_v = cv.vals_a; b.out_k = cv.keys_b; b.out_v = cv.vals_b;      // (the runs are sorted in place)
         b.n = (int)cap_img; b.n_dev = cv.sort_end; b.err = nullptr;
@@ -1585,17 +1549,9 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
         if (rc) return rc;
       }
     }
-    if (group_ok) {
-      // images with more than max_nms candidates: group the top max_nms (now in score order) by class, one stable pass
-      rc = seg_group_by_class(cv.keys_b, cv.keys_a, cv.vals_b, cv.vals_a, cv.grp_begin, cv.grp_end, (int)bs, cap_img, cv.cand, cv.srs_hist,
-                              cv.digit_base, st);
-      if (rc) return rc;
-      dim3 gc((unsigned)((max_nms + 255) / 256), (unsigned)bs);
-      k_copy_grouped<<<gc, 256, 0, st>>>(cv.keys_a, cv.keys_b, cv.vals_a, cv.vals_b, cv.grp_begin, cv.grp_end);
-    }
     const int64_t nseg = bs * ncs;
-    k_class_bounds<<<(unsigned)((nseg + 255) / 256), 256, 0, st>>>(cv.keys_b, cv.sort_begin, cv.img_end, cv.mode, cv.digit_base, (int)bs,
-                                                                   ncs, nv.seg_begin, nv.seg_end, nv.keep_cnt);
+    k_class_bounds<<<(unsigned)((nseg + 255) / 256), 256, 0, st>>>(cv.keys_b, cv.sort_begin, cv.img_end, cv.mode, (int)bs, ncs,
+                                                                   nv.seg_begin, nv.seg_end, nv.keep_cnt);
    }
    dim3 gp((unsigned)((max_seg + 255) / 256), (unsigned)bs);
    {
@@ -1612,7 +1568,7 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   a.ecap = nv.ecap; a.n = (int)(bs * cap_img); a.capmax = cap_max(bs * ncs);
   a.max_keep = (int)max_det; a.window = nms_window(max_det); a.thr = iou_thres; a.cull = (iou_thres >= 0.f) ? 1 : 0;
   // the output stage runs inside k_nms_small unless the caller wants packed rows (SmallGather)
-  const bool fused_out = small_nms && !out_packed && !no_fused_out;
+  const bool fused_out = small_nms && !out_packed;
   if (small_nms) {
     ProfScope ps(PROF_STEPS, st);
     static OncePerDevice attr;

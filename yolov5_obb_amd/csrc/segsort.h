@@ -150,20 +150,4 @@ static int seg_radix_sort_large(unsigned long long* ka, unsigned long long* kb, 
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 
-// One stable pass that groups a single-list range (already in score order; values = candidate slots of the image) by the
-// candidates' class: (kin, vin) -> (kout, vout); digit_base[g][c] receives the start of class c inside segment g.
-static int seg_group_by_class(const unsigned long long* kin, unsigned long long* kout, const uint32_t* vin, uint32_t* vout,
-                              const int* seg_begin, const int* seg_end, int nseg, long long cap, const float4* cand, uint32_t* hist,
-                              uint32_t* digit_base, hipStream_t st) {
-  SrsArgs a;
-  a.seg_begin = seg_begin; a.seg_end = seg_end; a.hist = hist;
-  a.tiles = (int)((cap + kSrsTile - 1) / kSrsTile);
-  a.shift = 0; a.cand = cand; a.cap_img = cap; a.digit_base = digit_base;
-  a.kin = kin; a.kout = kout; a.vin = vin; a.vout = vout;
-  dim3 gt((unsigned)a.tiles, (unsigned)nseg);
-  k_srs_hist<<<gt, kSrsThreads, 0, st>>>(a);
-  k_srs_scatter<<<gt, kSrsThreads, 0, st>>>(a);
-  return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
-}
-
 }  // namespace obb

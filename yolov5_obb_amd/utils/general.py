@@ -4,7 +4,6 @@
 kernels, host syncs and a device->host mask copy.
 """
 import ctypes as C
-import os
 import threading
 import time
 
@@ -15,7 +14,6 @@ from .. import _lib
 pi = 3.141592  # utils/general.py:34 (truncated on purpose: it is the constant the labels were encoded with)
 
 _MAX_WH = 4096      # utils/general.py:793
-_POLL_COUNTS = os.environ.get("OBB_NMS_POLL_COUNTS", "1") != "0"      # counts through polled pinned memory (see below)
 _PENDING = -(1 << 62)
 _POLL_SECONDS = 2e-3  # busy-poll this long (a bs16 step is ~0.2 ms), then yield the GIL between polls, then give up polling
 _POLL_GIVE_UP = 1.0   # ... after this many seconds: fall back to a stream synchronise
@@ -188,8 +186,8 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
         # Pinned host memory the last kernel writes straight into (the device reaches it through the same pointer), polled
         # by this thread: no copy kernel, no wake-up of a blocked stream wait.  (Device memory + one blocking copy: 0.254 ms
         # per bs16 step; pinned memory + stream synchronise: 0.282 ms.)
-        meta = torch.empty(bs + 2, dtype=torch.int64).pin_memory() if _POLL_COUNTS else torch.empty(bs + 2, dtype=torch.int64, device=dev)
-        _meta_memo[mkey] = meta = (meta, meta.numpy() if _POLL_COUNTS else None)
+        meta = torch.empty(bs + 2, dtype=torch.int64).pin_memory()
+        _meta_memo[mkey] = meta = (meta, meta.numpy())
     meta, meta_np = meta
     agn = int(bool(agnostic))
     capped = False                # obb_nms_set_max_grid is per calling thread (thread_local in the library): no other thread sees it
@@ -203,8 +201,7 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
             # the same for the NMS kernel: assume the small segments of that regime (a few hundred boxes per image and class);
             # a call that meets a larger one reports it (status[0] = -1) and is repeated on the persistent kernel
             seg_hint = int(_seg_memo.get(key, 1))
-            if meta_np is not None:
-                meta_np.fill(_PENDING)
+            meta_np.fill(_PENDING)
             with _lib.guard(dev):
                 st = _lib.stream_handle(dev)
                 wkey = (bs, cap, nc, agn, capped)          # (the library sizes the workspace from the calling thread's grid cap)
@@ -219,18 +216,15 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
                     (hint & 0xffffffff) | ((seg_hint & 0x1fffffff) << 32) | ((1 << 62) if _small_memo.get(key) else 0), _lib.ptr(out), 1, _lib.ptr(meta),
                     C.c_void_p(meta.data_ptr() + 8 * bs), _lib.ptr(ws), ws.numel(), C.c_void_p(st))
             _lib.check(rc, "obb_non_max_suppression_obb")
-            if meta_np is not None:                                   # every entry is one aligned 8-byte store of the last kernel
-                t_poll = time.perf_counter()
-                while meta_np.min() == _PENDING:
-                    waited = time.perf_counter() - t_poll
-                    if waited > _POLL_GIVE_UP:                        # something is badly wrong, or a very long call
-                        _lib.stream_sync(dev)
-                        break
-                    if waited > _POLL_SECONDS:                        # the stream still holds earlier work (the model's forward):
-                        time.sleep(0)                                 # let other Python threads (DataLoader, pin-memory) run
-                m = meta_np.tolist()
-            else:
-                m = meta.tolist()                                     # the single device->host sync of the call
+            t_poll = time.perf_counter()                              # every entry is one aligned 8-byte store of the last kernel
+            while meta_np.min() == _PENDING:
+                waited = time.perf_counter() - t_poll
+                if waited > _POLL_GIVE_UP:                            # something is badly wrong, or a very long call
+                    _lib.stream_sync(dev)
+                    break
+                if waited > _POLL_SECONDS:                            # the stream still holds earlier work (the model's forward):
+                    time.sleep(0)                                     # let other Python threads (DataLoader, pin-memory) run
+            m = meta_np.tolist()
             _small_memo[key] = bool((m[bs + 1] >> 62) & 1)                    # status[1]: bit 62 = boxes with a sub-pixel side were met,
             _small_memo[key, "resolved"] = bool((m[bs + 1] >> 61) & 1)        # bit 61 = ... and such an image kept its class segments
             seg_max, m[bs + 1] = (m[bs + 1] >> 32) & 0x1fffffff, m[bs + 1] & 0xffffffff       # largest segment | largest candidate count
