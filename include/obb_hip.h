@@ -297,6 +297,32 @@ int obb_non_max_suppression_obb_st(const void* pred, const void* objcol, int dty
                                    int64_t* out_count, int64_t* status, void* ws, size_t ws_bytes, void* state, size_t state_bytes,
                                    void* stream);
 
+/* The same call fed straight from the Detect head's 1x1-conv outputs instead of `pred`: Detect.forward (models/yolo.py:61-81)
+ * followed by non_max_suppression_obb (utils/general.py:772-862) as detect.py and val.py chain them, without the dense prediction
+ * tensor z (bs, A, no) and the permuted raw head x in between.
+ *   conv_out[l]  level l's conv output (bs, na*no, ny[l], nx[l]), contiguous, dtype 0 = fp32 / 1 = fp16; nl <= 4, na <=
+ *                OBB_LOSS_MAX_ANCHORS, no = 5 + nc + 180 with 1 <= nc <= 256 (the limits of obb_detect_decode_levels and
+ *                obb_non_max_suppression_obb)
+ *   anchors_px_host HOST [nl][na][2] = Detect.anchors * stride, strides_host HOST [nl]: as obb_detect_decode_levels takes them
+ * What is read: per (level, image, anchor) tile of 256 bytes of positions, the objectness line (channel a*no + 4) -- decoded exactly
+ * as z[..., 4] and compared with conf_thres in the tensor dtype (:785) -- and, only where some position of the tile passes, the
+ * tile's no channel lines, from which the passing rows are decoded with the arithmetic of obb_detect_decode (csrc/detect_math.h)
+ * and reduced as the filter kernel of obb_non_max_suppression_obb reduces rows of z.  Every candidate carries the index its row
+ * has in z (rows of level l start at sum over the levels before of na*ny*nx, then a*ny*nx + y*nx + x), so the sort keys, the score
+ * ties and the kept list are those of the eager chain: the result is bit-identical to obb_detect_decode_levels (z_out) followed by
+ * obb_non_max_suppression_obb_st on the same inputs and arguments.
+ * Workspace: obb_nms_obb_workspace_bytes(bs, cap_img, nc, agnostic) with A = sum of na*ny[l]*nx[l] -- nothing more.  Output contract,
+ * status words, hints and retry cases as obb_non_max_suppression_obb_st; `state` may be NULL (a reset launch zeroes the counters,
+ * as in obb_non_max_suppression_obb_col).  Everything before any device call answers OBB_ERR_BAD_ARG for an nl out of range,
+ * NULL tables or level pointers, an unknown dtype, nc or na out of range. */
+int obb_non_max_suppression_obb_head(int nl, const void* const* conv_out, int dtype, int64_t bs, int64_t na, int64_t no,
+                                     const int64_t* ny, const int64_t* nx, const float* anchors_px_host, const float* strides_host,
+                                     float conf_thres, float iou_thres, const int32_t* classes_host, int n_classes, int agnostic,
+                                     int multi_label, int64_t max_det, int64_t max_nms, float max_wh, const float* extra8,
+                                     int64_t n_extra, int64_t cap_img, int64_t expected_cand, float* out, int out_packed,
+                                     int64_t* out_count, int64_t* status, void* ws, size_t ws_bytes, void* state, size_t state_bytes,
+                                     void* stream);
+
 /* ------------------------------------------------------------------ training loss -------------------- */
 
 /*

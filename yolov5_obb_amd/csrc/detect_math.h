@@ -1,0 +1,37 @@
+// Per-element decode of the Detect head (models/yolo.py:71-74), shared by the Detect decode kernels (head.hip) and the NMS front
+// kernel that reads the conv outputs directly (nms_head.h): both must produce the same bits for every element.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
+#include "dtype_device.h"
+#include "loss_math.h"
+
+namespace obb {
+
+// y = x.sigmoid() in the tensor dtype, then (models/yolo.py:71-74, inplace branch)
+//   xy = (y*2 - 0.5 + grid) * stride     y*2 and -0.5 in the tensor dtype; grid is a float32 tensor -> fp32 from there
+//   wh = (y*2)**2 * anchor_grid          (y*2)**2 in the tensor dtype; anchor_grid is float32 -> fp32 product
+// and the result is rounded to the tensor dtype by the slice assignment.
+// sigmoid in the precision the comparison with the reference allows: fp32 tensors get the correctly rounded expf and
+// division; fp16 tensors are rounded to 11 bits right after, so the hardware exp2 / reciprocal (1 ulp of fp32 each) can
+// only move a result that sits within 2^-12 relative of an fp16 rounding boundary -- the same 1-ulp-of-fp16 freedom the
+// reference's own libm has (tests/test_head_gpu.py states the tolerance)
+template <typename T> __device__ __forceinline__ float detect_sigmoid(float x) { return sigmoid_f(x); }
+template <> __device__ __forceinline__ float detect_sigmoid<__half>(float x) {
+  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
+}
+
+template <typename T>
+__device__ __forceinline__ float detect_decode_one(float raw, int ch, float gx, float gy, float stride, float aw, float ah) {
+  const float y = round_to_dtype<T>(detect_sigmoid<T>(raw));
+  if (ch >= 4) return y;
+  const float t = round_to_dtype<T>(y * 2.0f);
+  if (ch < 2) {
+    const float u = round_to_dtype<T>(t - 0.5f);
+    return round_to_dtype<T>((u + (ch == 0 ? gx : gy)) * stride);
+  }
+  const float q = round_to_dtype<T>(t * t);
+  return round_to_dtype<T>(q * (ch == 2 ? aw : ah));
+}
+
+}  // namespace obb

@@ -1015,6 +1015,7 @@ static int run_nms_rot64(const double* dets5, const double* scores, int64_t n, f
 }  // namespace obb
 
 #include "nmsobb_impl.h"
+#include "nms_head.h"
 
 using namespace obb;
 
@@ -1149,6 +1150,43 @@ int obb_non_max_suppression_obb_st(const void* pred, const void* objcol, int dty
   return run_nms_obb(pred, objcol, dtype, bs, A, no, conf_thres, iou_thres, classes_host, n_classes, agnostic, multi_label, max_det,
                      max_nms, max_wh, extra8, n_extra, cap_img, expected_cand, out, out_packed ? 1 : 0, out_count, status, ws, ws_bytes,
                      (hipStream_t)stream, state, state_bytes);
+}
+
+int obb_non_max_suppression_obb_head(int nl, const void* const* conv_out, int dtype, int64_t bs, int64_t na, int64_t no,
+                                     const int64_t* ny, const int64_t* nx, const float* anchors_px_host, const float* strides_host,
+                                     float conf_thres, float iou_thres, const int32_t* classes_host, int n_classes, int agnostic,
+                                     int multi_label, int64_t max_det, int64_t max_nms, float max_wh, const float* extra8,
+                                     int64_t n_extra, int64_t cap_img, int64_t expected_cand, float* out, int out_packed,
+                                     int64_t* out_count, int64_t* status, void* ws, size_t ws_bytes, void* state, size_t state_bytes,
+                                     void* stream) {
+  // the limits of obb_detect_decode_levels and obb_non_max_suppression_obb, checked before anything is launched
+  const int64_t nc = no - 5 - 180;
+  if (nl < 1 || nl > kHeadMaxLevels || !conv_out || !ny || !nx || !anchors_px_host || !strides_host || bs < 1 || na < 1 ||
+      na > OBB_LOSS_MAX_ANCHORS || nc < 1 || nc > 256 || (dtype != 0 && dtype != 1) || bs * na > 65535)
+    return OBB_ERR_BAD_ARG;
+  const int TP = dtype == 0 ? kHeadTile<float> : kHeadTile<__half>;
+  const size_t esz = dtype == 0 ? 4 : 2;
+  HeadFront h;
+  h.nl = nl; h.na = (int)na; h.vec = 1;
+  int64_t A = 0, tiles = 0;
+  for (int l = 0; l < kHeadMaxLevels; l++) {
+    if (l >= nl) { h.in[l] = nullptr; h.ny[l] = h.nx[l] = 0; h.a_off[l] = A; h.tile_end[l] = (int)tiles; h.stride[l] = 0.f; continue; }
+    if (!conv_out[l] || ny[l] < 1 || nx[l] < 1 || ny[l] * nx[l] * na * no > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
+    const int64_t HW = ny[l] * nx[l];
+    h.in[l] = conv_out[l]; h.ny[l] = (int)ny[l]; h.nx[l] = (int)nx[l]; h.a_off[l] = A; h.stride[l] = strides_host[l];
+    for (int a = 0; a < OBB_LOSS_MAX_ANCHORS; a++) {
+      h.anchor_px[l][a][0] = a < na ? anchors_px_host[((size_t)l * na + a) * 2] : 0.f;
+      h.anchor_px[l][a][1] = a < na ? anchors_px_host[((size_t)l * na + a) * 2 + 1] : 0.f;
+    }
+    if ((((uintptr_t)conv_out[l]) & 15) != 0 || ((size_t)HW * esz) % 16 != 0) h.vec = 0;
+    tiles += (HW + TP - 1) / TP;
+    if (tiles > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
+    h.tile_end[l] = (int)tiles;
+    A += na * HW;
+  }
+  return run_nms_obb(nullptr, nullptr, dtype, bs, A, no, conf_thres, iou_thres, classes_host, n_classes, agnostic, multi_label, max_det,
+                     max_nms, max_wh, extra8, n_extra, cap_img, expected_cand, out, out_packed ? 1 : 0, out_count, status, ws, ws_bytes,
+                     (hipStream_t)stream, state, state_bytes, &h);
 }
 
 int obb_profile_enable(int on) {

@@ -1383,13 +1383,18 @@ static int obb_carve(void* base, int64_t bs, int64_t cap_img, int64_t ncs, ObbCa
   return OBB_OK;
 }
 
+// The front kernel that reads the Detect head's conv outputs instead of `pred` (nms_head.h, obb_non_max_suppression_obb_head)
+struct HeadFront;
+static int launch_decode_head(const HeadFront& h, const DecodeArgs& d, int dtype, hipStream_t st);
+
+// head != NULL: the candidates come from the conv outputs it describes (k_decode_head) and pred / objcol are not read
 static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t bs, int64_t A, int64_t no, float conf_thres, float iou_thres,
                        const int32_t* classes_host, int n_classes, int agnostic, int multi_label, int64_t max_det, int64_t max_nms,
                        float max_wh, const float* extra8, int64_t n_extra, int64_t cap_img, int64_t expected_cand, float* out,
                        int out_packed, int64_t* out_count, int64_t* status, void* ws, size_t ws_bytes, hipStream_t st, void* state = nullptr,
-                       size_t state_bytes = 0) {
+                       size_t state_bytes = 0, const HeadFront* head = nullptr) {
   const int nc = (int)(no - 5 - 180);                              // :784
-  if (bs < 1 || A < 1 || nc < 1 || nc > 256 || max_det < 1 || cap_img < 1 || !pred || !out || !out_count || !status)
+  if (bs < 1 || A < 1 || nc < 1 || nc > 256 || max_det < 1 || cap_img < 1 || (!pred && !head) || !out || !out_count || !status)
     return OBB_ERR_BAD_ARG;
   if (A * nc + n_extra > 0xffffffffLL || bs * cap_img > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
   if (dtype != 0 && dtype != 1) return OBB_ERR_BAD_ARG;
@@ -1448,7 +1453,10 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   dim3 gd((unsigned)((A + kDecThreads * d.rows_per_thread - 1) / (kDecThreads * d.rows_per_thread)), (unsigned)bs);
   {
     ProfScope ps(PROF_DECODE, st);
-    if (dtype == 0) k_decode<float><<<gd, kDecThreads, 0, st>>>(d);
+    if (head) {
+      rc = launch_decode_head(*head, d, dtype, st);
+      if (rc) return rc;
+    } else if (dtype == 0) k_decode<float><<<gd, kDecThreads, 0, st>>>(d);
     else k_decode<__half><<<gd, kDecThreads, 0, st>>>(d);
   }
   if (n_extra > 0 && extra8) k_append_extra<<<(unsigned)((n_extra + 255) / 256), 256, 0, st>>>(extra8, (int)n_extra, A, nc, d);

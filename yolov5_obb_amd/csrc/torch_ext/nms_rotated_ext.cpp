@@ -36,7 +36,7 @@ namespace {
 // ---------------------------------------------------------------- the C ABI, bound at run time
 #define OBB_API(X)                                                                                                         \
   X(obb_version) X(obb_nms_set_max_grid) X(obb_nms_workspace_bytes) X(obb_nms_rotated_f32) X(obb_nms_rotated_f64)       \
-  X(obb_nms_poly_f32) X(obb_nms_obb_workspace_bytes) X(obb_nms_obb_state_bytes) X(obb_non_max_suppression_obb_st)                                   \
+  X(obb_nms_poly_f32) X(obb_nms_obb_workspace_bytes) X(obb_nms_obb_state_bytes) X(obb_non_max_suppression_obb_st) X(obb_non_max_suppression_obb_head)                                   \
   X(obb_val_tail_batch_workspace_bytes) X(obb_val_tail_batch_rows_f32)
 
 struct Api {
@@ -266,58 +266,36 @@ void hint_set(int dev, int64_t A, int64_t nc, bool multi, double conf_thres, int
   if (seg >= 0) { e.seg = seg; e.hold_seg = 0; }
 }
 
-std::vector<at::Tensor> non_max_suppression_obb(const at::Tensor& prediction, double conf_thres, double iou_thres,
-                                                const c10::optional<std::vector<int64_t>>& classes, bool agnostic, bool multi_label,
-                                                const c10::optional<at::Tensor>& extra, int64_t max_det,
-                                                const c10::optional<at::Tensor>& objcol) {
-  need_api();
-  require_cuda(prediction, "prediction");
-  if (prediction.dim() != 3) throw std::runtime_error("prediction must be (bs, anchors, no)");
-  const int64_t nc = prediction.size(2) - 5 - kCsl;
-  if (nc < 1 || nc > 256) throw std::runtime_error("non_max_suppression_obb: 1 <= nc <= 256 supported, got nc = " + std::to_string(nc));
-  int dtype;
-  if (prediction.scalar_type() == at::kFloat) dtype = 0;
-  else if (prediction.scalar_type() == at::kHalf) dtype = 1;
-  else throw std::runtime_error(std::string("non_max_suppression_obb: float32 or float16 expected, got ") + c10::toString(prediction.scalar_type()));
-  const at::Tensor pred = prediction.contiguous();
-  const int64_t bs = pred.size(0), A = pred.size(1), no = pred.size(2);
-  const at::Device dev = pred.device();
-  const bool multi = multi_label && nc > 1;
-  std::vector<at::Tensor> result;
-  if (bs == 0) return result;
-  if (A == 0) {
-    at::Tensor z = at::zeros({0, 7}, at::TensorOptions().dtype(at::kFloat).device(dev));
-    result.assign((size_t)bs, z);
-    return result;
-  }
+// classes= and the label rows (utils/general.py:807-813, prepared by the Python layer as [img, x, y, l, s, theta, conf, cls]) as the
+// C ABI takes them; prepare() returns false for an empty class list (no detections at all)
+struct NmsOpts {
   std::vector<int32_t> cls;
-  if (classes.has_value()) {
-    if (classes->empty()) {
-      at::Tensor z = at::zeros({0, 7}, at::TensorOptions().dtype(at::kFloat).device(dev));
-      result.assign((size_t)bs, z);
-      return result;
-    }
-    for (int64_t c : *classes) cls.push_back((int32_t)c);
-  }
+  at::Tensor extra_c;
   const float* extra_p = nullptr;
   int64_t n_extra = 0;
-  at::Tensor extra_c;
-  if (extra.has_value() && extra->defined() && extra->numel() > 0) {
-    extra_c = extra->to(dev, at::kFloat).contiguous();
-    if (extra_c.dim() != 2 || extra_c.size(1) != 8) throw std::runtime_error("non_max_suppression_obb: label rows must be (n, 8)");
-    extra_p = extra_c.data_ptr<float>();
-    n_extra = extra_c.size(0);
+  bool prepare(const c10::optional<std::vector<int64_t>>& classes, const c10::optional<at::Tensor>& extra, const at::Device dev) {
+    if (classes.has_value()) {
+      if (classes->empty()) return false;
+      for (int64_t c : *classes) cls.push_back((int32_t)c);
+    }
+    if (extra.has_value() && extra->defined() && extra->numel() > 0) {
+      extra_c = extra->to(dev, at::kFloat).contiguous();
+      if (extra_c.dim() != 2 || extra_c.size(1) != 8) throw std::runtime_error("non_max_suppression_obb: label rows must be (n, 8)");
+      extra_p = extra_c.data_ptr<float>();
+      n_extra = extra_c.size(0);
+    }
+    return true;
   }
-  const void* col_p = nullptr;
-  if (objcol.has_value() && objcol->defined()) {
-    const at::Tensor& c = *objcol;
-    if (c.dim() == 2 && c.size(0) == bs && c.size(1) == A && c.scalar_type() == pred.scalar_type() && c.device() == dev && c.is_contiguous() &&
-        pred.data_ptr() == prediction.data_ptr())
-      col_p = c.data_ptr();
-  }
+};
 
+// The call loop of both fused entries (obb_non_max_suppression_obb_st, obb_non_max_suppression_obb_head): workspace, caller-kept
+// state, polled counters, the retry cases of include/obb_hip.h and the hint memo of the shape.  launch(cap_img, expected_cand, out,
+// out_count, status, ws, ws_bytes, state, state_bytes, stream) makes one call of the entry with out_packed = 0.
+template <class Launch>
+std::vector<at::Tensor> run_fused(const at::Device dev, int64_t bs, int64_t A, int64_t nc, bool multi, double conf_thres, bool agnostic,
+                                  int64_t max_det, int64_t n_extra, Launch&& launch) {
+  std::vector<at::Tensor> result;
   static thread_local std::map<std::tuple<int64_t, int64_t, int64_t, int, bool>, size_t> ws_memo;
-  const float conf_f = (float)conf_thres;
   ShapeMemo& memo = shape_memos()[ShapeKey{(int)dev.index(), A, nc, multi, conf_key(conf_thres)}];
   const int64_t worst = A * (multi ? nc : 1) + n_extra;
   int64_t cap = std::min(worst, std::max<int64_t>(memo.cap, 65536));
@@ -339,11 +317,8 @@ std::vector<at::Tensor> non_max_suppression_obb(const at::Tensor& prediction, do
     if (!sb.clean) sb.t.zero_();                                       // the previous call on it did not complete
     sb.clean = false;
     arm(meta);
-    const int rc = api.obb_non_max_suppression_obb_st(pred.data_ptr(), col_p, dtype, bs, A, no, conf_f, (float)iou_thres, cls.empty() ? nullptr : cls.data(),
-                                                       (int)cls.size(), agnostic ? 1 : 0, multi ? 1 : 0, max_det, kMaxNms, (float)kMaxWh, extra_p, n_extra, cap,
-                                                       hint | (seg_hint << 32) | (memo.small_boxes ? (int64_t(1) << 62) : 0), out.data_ptr<float>(), 0, meta.p, meta.p + bs,
-                                                       ws.data_ptr(), (size_t)ws.numel(), sb.t.data_ptr(), (size_t)sb.t.numel(),
-                                                       stream.stream());
+    const int rc = launch(cap, hint | (seg_hint << 32) | (memo.small_boxes ? (int64_t(1) << 62) : 0), out.data_ptr<float>(), meta.p, meta.p + bs,
+                          ws.data_ptr(), (size_t)ws.numel(), sb.t.data_ptr(), (size_t)sb.t.numel(), stream.stream());
     check(rc, "obb_non_max_suppression_obb");
     {
       py::gil_scoped_release nogil;
@@ -388,6 +363,108 @@ std::vector<at::Tensor> non_max_suppression_obb(const at::Tensor& prediction, do
   result.reserve((size_t)bs);
   for (int64_t b = 0; b < bs; b++) result.push_back(view_of(out, b * max_det * 7, {meta.p[b], 7}, {7, 1}));
   return result;
+}
+
+std::vector<at::Tensor> non_max_suppression_obb(const at::Tensor& prediction, double conf_thres, double iou_thres,
+                                                const c10::optional<std::vector<int64_t>>& classes, bool agnostic, bool multi_label,
+                                                const c10::optional<at::Tensor>& extra, int64_t max_det,
+                                                const c10::optional<at::Tensor>& objcol) {
+  need_api();
+  require_cuda(prediction, "prediction");
+  if (prediction.dim() != 3) throw std::runtime_error("prediction must be (bs, anchors, no)");
+  const int64_t nc = prediction.size(2) - 5 - kCsl;
+  if (nc < 1 || nc > 256) throw std::runtime_error("non_max_suppression_obb: 1 <= nc <= 256 supported, got nc = " + std::to_string(nc));
+  int dtype;
+  if (prediction.scalar_type() == at::kFloat) dtype = 0;
+  else if (prediction.scalar_type() == at::kHalf) dtype = 1;
+  else throw std::runtime_error(std::string("non_max_suppression_obb: float32 or float16 expected, got ") + c10::toString(prediction.scalar_type()));
+  const at::Tensor pred = prediction.contiguous();
+  const int64_t bs = pred.size(0), A = pred.size(1), no = pred.size(2);
+  const at::Device dev = pred.device();
+  const bool multi = multi_label && nc > 1;
+  std::vector<at::Tensor> result;
+  if (bs == 0) return result;
+  if (A == 0) {
+    at::Tensor z = at::zeros({0, 7}, at::TensorOptions().dtype(at::kFloat).device(dev));
+    result.assign((size_t)bs, z);
+    return result;
+  }
+  NmsOpts o;
+  if (!o.prepare(classes, extra, dev)) {
+    result.assign((size_t)bs, at::zeros({0, 7}, at::TensorOptions().dtype(at::kFloat).device(dev)));
+    return result;
+  }
+  const std::vector<int32_t>& cls = o.cls;
+  const float* extra_p = o.extra_p;
+  const int64_t n_extra = o.n_extra;
+  const void* col_p = nullptr;
+  if (objcol.has_value() && objcol->defined()) {
+    const at::Tensor& c = *objcol;
+    if (c.dim() == 2 && c.size(0) == bs && c.size(1) == A && c.scalar_type() == pred.scalar_type() && c.device() == dev && c.is_contiguous() &&
+        pred.data_ptr() == prediction.data_ptr())
+      col_p = c.data_ptr();
+  }
+
+  return run_fused(dev, bs, A, nc, multi, conf_thres, agnostic, max_det, n_extra,
+                   [&](int64_t cap, int64_t hint_word, float* out, int64_t* counts, int64_t* status, void* ws, size_t ws_bytes, void* state,
+                       size_t state_bytes, hipStream_t st) {
+                     return api.obb_non_max_suppression_obb_st(pred.data_ptr(), col_p, dtype, bs, A, no, (float)conf_thres, (float)iou_thres,
+                                                               cls.empty() ? nullptr : cls.data(), (int)cls.size(), agnostic ? 1 : 0, multi ? 1 : 0,
+                                                               max_det, kMaxNms, (float)kMaxWh, extra_p, n_extra, cap, hint_word, out, 0, counts,
+                                                               status, ws, ws_bytes, state, state_bytes, st);
+                   });
+}
+
+// Detect.forward + non_max_suppression_obb straight from the conv outputs (obb_non_max_suppression_obb_head): the lazy outputs of
+// Detect.lazy_nms (models/yolo.py).  convs[l] (bs, na*no, ny, nx) contiguous; anchors_px [nl][na][2] flattened (anchors * stride),
+// strides [nl].  Same loop, hints and result as non_max_suppression_obb of the prediction tensor Detect would have built.
+std::vector<at::Tensor> non_max_suppression_obb_head(const std::vector<at::Tensor>& convs, const std::vector<float>& anchors_px,
+                                                     const std::vector<float>& strides, double conf_thres, double iou_thres,
+                                                     const c10::optional<std::vector<int64_t>>& classes, bool agnostic, bool multi_label,
+                                                     const c10::optional<at::Tensor>& extra, int64_t max_det) {
+  need_api();
+  const int nl = (int)convs.size();
+  if (nl < 1 || nl > 4 || (int64_t)strides.size() != nl || anchors_px.empty() || anchors_px.size() % (2 * nl) != 0)
+    throw std::runtime_error("non_max_suppression_obb_head: 1..4 levels with anchors_px [nl][na][2] and strides [nl] expected");
+  const at::Tensor& c0 = convs[0];
+  require_cuda(c0, "convs[0]");
+  const int64_t na = (int64_t)anchors_px.size() / (2 * nl);
+  if (c0.dim() != 4 || c0.size(1) % na != 0) throw std::runtime_error("non_max_suppression_obb_head: conv outputs (bs, na*no, ny, nx) expected");
+  const int64_t bs = c0.size(0), no = c0.size(1) / na, nc = no - 5 - kCsl;
+  if (nc < 1 || nc > 256) throw std::runtime_error("non_max_suppression_obb: 1 <= nc <= 256 supported, got nc = " + std::to_string(nc));
+  int dtype;
+  if (c0.scalar_type() == at::kFloat) dtype = 0;
+  else if (c0.scalar_type() == at::kHalf) dtype = 1;
+  else throw std::runtime_error(std::string("non_max_suppression_obb: float32 or float16 expected, got ") + c10::toString(c0.scalar_type()));
+  const at::Device dev = c0.device();
+  std::vector<const void*> ptrs;
+  std::vector<int64_t> ny, nx;
+  int64_t A = 0;
+  for (const at::Tensor& c : convs) {
+    if (c.device() != dev || c.scalar_type() != c0.scalar_type() || c.dim() != 4 || c.size(0) != bs || c.size(1) != na * no || !c.is_contiguous())
+      throw std::runtime_error("non_max_suppression_obb_head: conv outputs of one device, dtype, batch and channel count, contiguous, expected");
+    ptrs.push_back(c.data_ptr());
+    ny.push_back(c.size(2));
+    nx.push_back(c.size(3));
+    A += na * c.size(2) * c.size(3);
+  }
+  const bool multi = multi_label && nc > 1;
+  std::vector<at::Tensor> result;
+  if (bs == 0) return result;
+  NmsOpts o;
+  if (!o.prepare(classes, extra, dev)) {
+    result.assign((size_t)bs, at::zeros({0, 7}, at::TensorOptions().dtype(at::kFloat).device(dev)));
+    return result;
+  }
+  return run_fused(dev, bs, A, nc, multi, conf_thres, agnostic, max_det, o.n_extra,
+                   [&](int64_t cap, int64_t hint_word, float* out, int64_t* counts, int64_t* status, void* ws, size_t ws_bytes, void* state,
+                       size_t state_bytes, hipStream_t st) {
+                     return api.obb_non_max_suppression_obb_head(nl, ptrs.data(), dtype, bs, na, no, ny.data(), nx.data(), anchors_px.data(),
+                                                                 strides.data(), (float)conf_thres, (float)iou_thres,
+                                                                 o.cls.empty() ? nullptr : o.cls.data(), (int)o.cls.size(), agnostic ? 1 : 0,
+                                                                 multi ? 1 : 0, max_det, kMaxNms, (float)kMaxWh, o.extra_p, o.n_extra, cap,
+                                                                 hint_word, out, 0, counts, status, ws, ws_bytes, state, state_bytes, st);
+                   });
 }
 
 // ---------------------------------------------------------------- the post-NMS tail of val.py for a batch (val.py:209-250)
@@ -559,6 +636,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("non_max_suppression_obb", &non_max_suppression_obb, py::arg("prediction"), py::arg("conf_thres") = 0.25, py::arg("iou_thres") = 0.45,
         py::arg("classes") = py::none(), py::arg("agnostic") = false, py::arg("multi_label") = false, py::arg("extra") = py::none(),
         py::arg("max_det") = 1500, py::arg("objcol") = py::none());
+  m.def("non_max_suppression_obb_head", &non_max_suppression_obb_head, py::arg("convs"), py::arg("anchors_px"), py::arg("strides"),
+        py::arg("conf_thres") = 0.25, py::arg("iou_thres") = 0.45, py::arg("classes") = py::none(), py::arg("agnostic") = false,
+        py::arg("multi_label") = false, py::arg("extra") = py::none(), py::arg("max_det") = 1500);
   m.def("abort_retries", []() { return (long long)g_abort_retries.load(std::memory_order_relaxed); },
         "calls of this process that a barrier time-out of the persistent NMS kernel sent to the 8-workgroup grid");
   m.def("hints_clear", &hints_clear, "forget the hint memo of the calling thread");

@@ -19,6 +19,10 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from ..lazy import LazyTensor
+
+_LAZY_MAX_LEVELS = 4         # include/obb_hip.h obb_non_max_suppression_obb_head: nl <= 4
+_LAZY_MAX_ANCHORS = 8        # ... na <= OBB_LOSS_MAX_ANCHORS
 
 
 class Detect(nn.Module):
@@ -33,6 +37,9 @@ class Detect(nn.Module):
     # store z[..., 4] densely next to z for the confidence filter of non_max_suppression_obb (module docstring)
     couple_nms = True
     fused_levels = True      # all levels decoded by one launch (obb_detect_decode_levels); False: one launch per level
+    # return z and x as lazy tensors (yolov5_obb_amd/lazy.py) that non_max_suppression_obb reads straight from the conv outputs
+    # (obb_non_max_suppression_obb_head): nothing of size (bs, A, no) is written unless something else touches them
+    lazy_nms = False
 
     def __init__(self, nc=80, anchors=(), ch=(), inplace=True):  # detection layer
         super().__init__()
@@ -109,6 +116,11 @@ class Detect(nn.Module):
         bs = c0.shape[0]
         shapes = [(c.shape[2], c.shape[3]) for c in convs]
         a_total = sum(self.na * ny * nx for ny, nx in shapes)
+        if self._lazy_possible(convs):
+            for i, (ny, nx) in enumerate(shapes):
+                if self.onnx_dynamic or self.grid[i].shape[2:4] != (ny, nx):
+                    self.grid[i], self.anchor_grid[i] = self._make_grid(nx, ny, i)
+            return _lazy_outputs(convs, code, self.na, self.no, anchor_px, strides, a_total, x)
         z = torch.empty((bs, a_total, self.no), dtype=c0.dtype, device=c0.device)
         col = torch.empty((bs, a_total), dtype=c0.dtype, device=c0.device) if self.couple_nms else None
         L = _lib.lib()
@@ -144,9 +156,83 @@ class Detect(nn.Module):
             z._obb_objcol = (col, z._version)
         return z, x
 
+    def _lazy_possible(self, convs):
+        """lazy_nms applies: eval mode on the GPU (checked by the caller), grad disabled, version counters present (not under
+        torch.inference_mode(), like couple_nms), and the limits of obb_non_max_suppression_obb_head."""
+        return (self.lazy_nms and not torch.is_grad_enabled() and not torch.is_inference_mode_enabled()
+                and not any(torch.is_inference(c) for c in convs) and 1 <= self.nl <= _LAZY_MAX_LEVELS
+                and 1 <= self.na <= _LAZY_MAX_ANCHORS and 1 <= self.nc <= 256)
+
     def _make_grid(self, nx=20, ny=20, i=0):  # models/yolo.py:83-92
         d = self.anchors[i].device
         yv, xv = torch.meshgrid([torch.arange(ny, device=d), torch.arange(nx, device=d)], indexing='ij')
         grid = torch.stack((xv, yv), 2).expand((1, self.na, ny, nx, 2)).float()
         anchor_grid = (self.anchors[i].clone() * self.stride[i]).view((1, self.na, 1, 1, 2)).expand((1, self.na, ny, nx, 2)).float()
         return grid, anchor_grid
+
+
+class LazyHead:
+    """What a lazy Detect output keeps: the conv outputs with the version counters they had at forward time, and the host
+    anchor / stride tables.  The values the outputs stand for were fixed at forward time: once a conv output has been
+    modified in place they are gone, and any use of the outputs raises."""
+
+    def __init__(self, convs, code, na, no, anchor_px, strides):
+        self.convs = convs
+        self.versions = [c._version for c in convs]
+        self.code, self.na, self.no = code, na, no
+        self.nl = len(convs)
+        self.anchor_px = [float(v) for a in anchor_px for v in a]       # [nl][na][2] flattened
+        self.strides = [float(s) for s in strides[:self.nl]]
+
+    def check(self):
+        if [c._version for c in self.convs] != self.versions:
+            raise RuntimeError("Detect (lazy_nms): a conv output was modified in place after forward(); the prediction it stood "
+                               "for is gone -- keep the conv outputs unchanged until the outputs are used, or set lazy_nms = False")
+
+    def decode(self, z=None, level=None, xp=None):
+        """Run the Detect decode into z (all levels) or into the permuted raw head xp of one level (obb_detect_decode_levels /
+        obb_detect_decode_col with only that output non-NULL)."""
+        self.check()
+        L = _lib.lib()
+        c0 = self.convs[0]
+        bs, nl, na = c0.shape[0], self.nl, self.na
+        with torch.cuda.device(c0.device):
+            st = _lib.stream_ptr(c0.device)
+            if z is not None:
+                rc = L.obb_detect_decode_levels(nl, (C.c_void_p * nl)(*[c.data_ptr() for c in self.convs]), self.code, bs, na, self.no,
+                                                (C.c_int64 * nl)(*[c.shape[2] for c in self.convs]),
+                                                (C.c_int64 * nl)(*[c.shape[3] for c in self.convs]),
+                                                (C.c_float * len(self.anchor_px))(*self.anchor_px), (C.c_float * nl)(*self.strides),
+                                                None, _lib.ptr(z), z.shape[1], None, st)
+                _lib.check(rc, "obb_detect_decode_levels")
+            else:
+                c = self.convs[level]
+                px = (C.c_float * (2 * na))(*self.anchor_px[2 * na * level:2 * na * (level + 1)])
+                rc = L.obb_detect_decode_col(_lib.ptr(c), self.code, bs, na, self.no, c.shape[2], c.shape[3], C.cast(px, C.c_void_p),
+                                             self.strides[level], _lib.ptr(xp), None, 0, 0, None, st)
+                _lib.check(rc, "obb_detect_decode_col")
+
+
+def _lazy_outputs(convs, code, na, no, anchor_px, strides, a_total, x):
+    """(lazy z, [lazy x_i]) of Detect.forward's inference branch; nothing is launched here."""
+    head = LazyHead(convs, code, na, no, anchor_px, strides)
+    c0 = convs[0]
+    bs, dt, dev = c0.shape[0], c0.dtype, c0.device
+
+    def make_z():
+        z = torch.empty((bs, a_total, no), dtype=dt, device=dev)
+        head.decode(z=z)
+        return z
+
+    def make_x(i):
+        def run():
+            c = convs[i]
+            xp = torch.empty((bs, na, c.shape[2], c.shape[3], no), dtype=dt, device=dev)
+            head.decode(level=i, xp=xp)
+            return xp
+        return run
+
+    z = LazyTensor((bs, a_total, no), dt, dev, make_z, payload=head)
+    for i, c in enumerate(convs):
+        x[i] = LazyTensor((bs, na, c.shape[2], c.shape[3], no), dt, dev, make_x(i))
+    return z, x

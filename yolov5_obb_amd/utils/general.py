@@ -10,6 +10,7 @@ import time
 import torch
 
 from .. import _lib
+from ..lazy import LazyTensor
 
 pi = 3.141592  # utils/general.py:34 (truncated on purpose: it is the constant the labels were encoded with)
 
@@ -130,6 +131,14 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
     Returns:
         list of detections, len=batch_size, on (n,7) tensor per image [xylsθ, conf, cls] θ ∈ [-pi/2, pi/2)
     """
+    head = None
+    if isinstance(prediction, LazyTensor):
+        # Detect.lazy_nms: never touched -> the fused entry on the conv outputs; materialised -> the real tensor, plain path
+        head = prediction.payload
+        if head is None:
+            prediction = prediction.materialize()
+        else:
+            head.check()
     _lib.require_cuda(prediction, "prediction")
     if prediction.dim() != 3:
         raise RuntimeError(f"prediction must be (bs, anchors, no), got {tuple(prediction.shape)}")
@@ -148,7 +157,7 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
     pred = prediction.contiguous()
     bs, A, no = pred.shape
     dev = pred.device
-    col = _objectness_column(prediction, pred)
+    col = _objectness_column(prediction, pred) if head is None else None
     multi = bool(multi_label) and nc > 1
     if bs == 0:
         return []
@@ -162,6 +171,9 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
         cl = None
         if classes is not None:
             cl = [int(c) for c in (classes if isinstance(classes, (list, tuple)) else list(classes))]
+        if head is not None:
+            return ext.non_max_suppression_obb_head(head.convs, head.anchor_px, head.strides, float(conf_thres), float(iou_thres), cl,
+                                                    bool(agnostic), multi, extra, int(max_det))
         return ext.non_max_suppression_obb(pred, float(conf_thres), float(iou_thres), cl, bool(agnostic), multi, extra, int(max_det), col)
     n_extra = 0 if extra is None else extra.shape[0]
     cls_arr = None
@@ -174,11 +186,38 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
     else:
         n_cls = 0
 
+    L = _lib.lib()
+    max_det = int(max_det)
+    cls_p = C.cast(cls_arr, C.c_void_p) if cls_arr is not None else C.c_void_p(0)
+    agn = int(bool(agnostic))
+    if head is None:
+        def launch(cap, hint_word, out, counts, status, ws, st):
+            return L.obb_non_max_suppression_obb_col(
+                _lib.ptr(pred), _lib.ptr(col), dtype, bs, A, no, float(conf_thres), float(iou_thres), cls_p, n_cls, agn, int(multi),
+                max_det, _MAX_NMS, float(_MAX_WH), _lib.ptr(extra), n_extra, cap, hint_word, out, 1, counts, status, _lib.ptr(ws), ws.numel(), C.c_void_p(st))
+    else:
+        nl = head.nl
+        conv_arr = (C.c_void_p * nl)(*[c.data_ptr() for c in head.convs])
+        ny_arr = (C.c_int64 * nl)(*[c.shape[2] for c in head.convs])
+        nx_arr = (C.c_int64 * nl)(*[c.shape[3] for c in head.convs])
+        px_arr = (C.c_float * len(head.anchor_px))(*head.anchor_px)
+        st_arr = (C.c_float * nl)(*head.strides)
+
+        def launch(cap, hint_word, out, counts, status, ws, st):
+            return L.obb_non_max_suppression_obb_head(
+                nl, conv_arr, dtype, bs, head.na, no, ny_arr, nx_arr, px_arr, st_arr, float(conf_thres), float(iou_thres), cls_p, n_cls,
+                agn, int(multi), max_det, _MAX_NMS, float(_MAX_WH), _lib.ptr(extra), n_extra, cap, hint_word, out, 1, counts, status,
+                _lib.ptr(ws), ws.numel(), None, 0, C.c_void_p(st))
+    return _run_fused(launch, dev, bs, A, nc, multi, conf_thres, n_extra, agn, max_det)
+
+
+def _run_fused(launch, dev, bs, A, nc, multi, conf_thres, n_extra, agn, max_det):
+    """The ctypes binding's call loop around one fused entry (launch: obb_non_max_suppression_obb_col or _head): workspace,
+    polled counters, the retry cases of include/obb_hip.h and the hint memo of the shape."""
+    L = _lib.lib()
     worst = A * (nc if multi else 1) + n_extra
     key = _key(dev.index, A, nc, multi, conf_thres)
     cap = min(worst, max(_cap_memo.get(key, 0), 65536))
-    L = _lib.lib()
-    max_det = int(max_det)
     out = torch.empty((bs * max_det, 7), dtype=torch.float32, device=dev)   # packed: image b's rows follow image b-1's
     mkey = (dev.index, bs, threading.get_ident())
     meta = _meta_memo.get(mkey)                                       # counts[bs] + status[2]: read back before returning,
@@ -189,7 +228,6 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
         meta = torch.empty(bs + 2, dtype=torch.int64).pin_memory()
         _meta_memo[mkey] = meta = (meta, meta.numpy())
     meta, meta_np = meta
-    agn = int(bool(agnostic))
     capped = False                # obb_nms_set_max_grid is per calling thread (thread_local in the library): no other thread sees it
     try:
         while True:
@@ -209,12 +247,8 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
                 if nbytes is None:
                     nbytes = _ws_memo[wkey] = L.obb_nms_obb_workspace_bytes(bs, cap, nc, agn)
                 ws = _lib.workspace(nbytes, dev, st)
-                rc = L.obb_non_max_suppression_obb_col(
-                    _lib.ptr(pred), _lib.ptr(col), dtype, bs, A, no, float(conf_thres), float(iou_thres),
-                    C.cast(cls_arr, C.c_void_p) if cls_arr is not None else C.c_void_p(0), n_cls, agn, int(multi),
-                    max_det, _MAX_NMS, float(_MAX_WH), _lib.ptr(extra), n_extra, cap,
-                    (hint & 0xffffffff) | ((seg_hint & 0x1fffffff) << 32) | ((1 << 62) if _small_memo.get(key) else 0), _lib.ptr(out), 1, _lib.ptr(meta),
-                    C.c_void_p(meta.data_ptr() + 8 * bs), _lib.ptr(ws), ws.numel(), C.c_void_p(st))
+                rc = launch(cap, (hint & 0xffffffff) | ((seg_hint & 0x1fffffff) << 32) | ((1 << 62) if _small_memo.get(key) else 0),
+                            _lib.ptr(out), _lib.ptr(meta), C.c_void_p(meta.data_ptr() + 8 * bs), ws, st)
             _lib.check(rc, "obb_non_max_suppression_obb")
             t_poll = time.perf_counter()                              # every entry is one aligned 8-byte store of the last kernel
             while meta_np.min() == _PENDING:
