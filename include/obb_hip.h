@@ -260,6 +260,12 @@ int64_t obb_task1_format_rows(const char* text_host, const int32_t* name_off_hos
  *               `ws` in a per-stream cache.)
  * Score ties are ordered by ascending (anchor*nc + class): deterministic, where the reference inherits the order
  * of torch's unstable sort.
+ * Non-finite inputs (NaN of either sign or payload, +-inf) give what the reference's torch ops give: a row passes the confidence
+ * filter iff obj > conf_thres (NaN and -inf fail, +inf passes; conf_thres rounded to the input dtype first); conf = obj * cls in
+ * the input dtype (0 * inf = NaN); the best class (multi_label = 0) and the CSL angle bin are the FIRST maximum with every NaN
+ * ranked above +inf (torch.max / torch.argmax), so a NaN best confidence drops the row (NaN > conf_thres is false) and a NaN bin is
+ * the angle; a box is too small iff min(l, s) < 0.001 with torch.min's NaN propagation (a NaN side keeps the box); NaN / inf
+ * coordinates send the image down the single list and reach the NMS unchanged.  The same holds for the _col, _st and _head entries.
  */
 #define OBB_NMS_SMALL_SEG 384
 #define OBB_NMS_SORT_LDS_HINT 6144

@@ -15,6 +15,7 @@
 #include <string.h>
 #include <hip/hip_fp16.h>
 #include "launch_once.h"
+#include "obb_device.h"
 #include "nms_core.h"
 #include "nms_mk.h"
 #include "obb_hip.h"
@@ -103,9 +104,8 @@ __device__ __forceinline__ void local_extras(const LocalExtras& x, const float* 
     float w = 0.f, h = 0.f;
     if (drop_small || x.bbpart != nullptr) { w = dets5[(size_t)i * 5 + 2]; h = dets5[(size_t)i * 5 + 3]; }
     if (drop_small) {
-      // nms_rotated_wrapper.py:32  too_small = dets[:, [2, 3]].min(1)[0] < 0.001   (torch.min propagates NaN; NaN < 0.001 is False)
-      float mn = (h < w) ? h : w;
-      if (mn < 0.001f) { *key_out = 0xFFFFFFFFu; ok = false; }
+      // nms_rotated_wrapper.py:32  too_small = dets[:, [2, 3]].min(1)[0] < 0.001   (NaN in either side: kept, obb_device.h)
+      if (box_too_small(w, h)) { *key_out = 0xFFFFFFFFu; ok = false; }
     }
     if (x.bbpart != nullptr && ok) {
       // bounding box of the finite centres of the boxes that take part: the extent of the data for the spatial index
@@ -218,8 +218,7 @@ __global__ __launch_bounds__(256) void k_prep_rot(const float* __restrict__ dets
     RotGeom::pack(f, q);
 #pragma unroll
     for (int k = 0; k < 4; k++) rec[(size_t)p * 4 + k] = q[k];
-    float mn = (h < w) ? h : w;
-    ok = !(drop_small && mn < 0.001f);
+    ok = !(drop_small && box_too_small(w, h));
     r = q[0].z; ms2 = q[0].w;
   }
   const u64 m = __ballot(ok);
@@ -281,8 +280,7 @@ __global__ void k_make_keys_f64(const double* __restrict__ scores, const double*
   uint64_t k = score_desc_key64(scores[i]);
   if (drop_small) {
     const double w = dets5[(size_t)i * 5 + 2], h = dets5[(size_t)i * 5 + 3];
-    const double mn = (h < w) ? h : w;
-    if (mn < 0.001) k = ~0ull;                             // nms_rotated_wrapper.py:32, compared in the tensor's dtype
+    if (box_too_small(w, h)) k = ~0ull;                           // nms_rotated_wrapper.py:32, compared in the tensor's dtype
   }
   keys[i] = k;
   vals[i] = (uint32_t)i;
@@ -298,8 +296,7 @@ __global__ __launch_bounds__(256) void k_prep_rot64(const double* __restrict__ d
     RotGeom64::pack(x, y, w, h, a, q);
 #pragma unroll
     for (int k = 0; k < RotGeom64::RECQ; k++) rec[(size_t)p * RotGeom64::RECQ + k] = q[k];
-    const double mn = (h < w) ? h : w;
-    ok = !(drop_small && mn < 0.001);
+    ok = !(drop_small && box_too_small(w, h));
   }
   const u64 m = __ballot(ok);
   if ((threadIdx.x & 63) == 0 && (p & ~63) < n) alive[p >> 6] = m;

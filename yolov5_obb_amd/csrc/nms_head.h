@@ -197,17 +197,17 @@ __global__ __launch_bounds__(kHeadThreads) void k_decode_head(DecodeArgs a, Head
       staged += np;
     };
     // class confidences (:820 conf = obj * cls in the input dtype)
-    float bestv = -__builtin_inff(); int besti = 0x7fffffff;
+    unsigned long long bestk = argmax_key(-__builtin_inff(), 0x7fffffff);
     for (int g = 0; g < ncg; g++) {
       const int c = g * 16 + l16;
       const float raw = (valid && c < a.nc) ? round_to_dtype<T>(detect_sigmoid<T>(head_ld<T>(s_tile, 5 + c, p))) : 0.f;
       const float v = (valid && c < a.nc) ? mul_in_dtype<T>(raw, obj) : -__builtin_inff();
       if (a.multi_label) stage(valid && c < a.nc && v > thr && class_allowed(a.cm, c), v, c);             // :827, :835
-      else if (c < a.nc && v > bestv) { bestv = v; besti = c; }           // a lane sees ascending c: first max kept
+      else if (c < a.nc) { const unsigned long long kk = argmax_key(v, c); bestk = kk > bestk ? kk : bestk; }   // a NaN wins
     }
     if (!a.multi_label) {
       float bv; int bi;
-      argmax_unkey(row_max_u64(argmax_key(bestv, besti)), bv, bi);                                            // :830
+      argmax_unkey(row_max_u64(bestk), bv, bi);                         // :830 (a NaN maximum fails bv > thr: the row is dropped)
       stage(valid && l16 == 0 && bv > thr && class_allowed(a.cm, bi), bv, bi);                                // :831, :835
     }
   }

@@ -28,6 +28,7 @@
 // The only host<->device traffic is the caller reading the bs counts (+ the overflow word) afterwards.
 #pragma once
 #include "dtype_device.h"
+#include "obb_device.h"
 #include "segsort.h"
 
 namespace obb {
@@ -44,13 +45,14 @@ template <> __device__ __forceinline__ float thr_in_dtype<float>(float t) { retu
 template <> __device__ __forceinline__ float thr_in_dtype<__half>(float t) { return __half2float(__float2half_rn(t)); }
 
 // wave arg-max with "first maximum" tie rule (torch.max over a dimension: utils/general.py:822, :830).  Value and index
-// travel as ONE 64-bit key -- order-preserving image of the float in the high word (-0 counts as +0; a NaN ranks above
-// everything, as in torch), ~index in the low word -- so the reduction is a plain unsigned max: four DPP steps inside the
+// travel as ONE 64-bit key -- order-preserving image of the float in the high word (-0 counts as +0; every NaN, of either
+// sign and any payload, maps to the one key 0xFFFFFFFF above +inf: torch.max / torch.argmax rank a NaN as the maximum and
+// take the first of several), ~index in the low word -- so the reduction is a plain unsigned max: four DPP steps inside the
 // 16-lane rows (quad swaps, half-row and row mirrors: a few cycles each, where ds_bpermute costs an LDS round trip per
 // step), then the four row results meet through v_readlane.
 __device__ __forceinline__ unsigned long long argmax_key(float v, int i) {
   const uint32_t b = __float_as_uint(v + 0.0f);
-  const uint32_t m = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  const uint32_t m = (v != v) ? 0xFFFFFFFFu : (b & 0x80000000u) ? ~b : (b | 0x80000000u);   // (unkeyed: a NaN)
   return ((unsigned long long)m << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
 }
 template <int CTRL>
@@ -122,7 +124,7 @@ __host__ __device__ __forceinline__ bool img_single_list(int t) {
   return (t & kImgWide) || ((t & kImgSmall) && (!(t & kImgChecked) || (t & kImgCross)));
 }
 __device__ __forceinline__ int cand_flags(float x, float l, float s, float win_lo, float win_hi) {
-  const float mn = (s < l) ? s : l;
+  const float mn = min_nan(l, s);
   const float rr = sqrtf(l * l + s * s) * 0.501f + 0.5f;
   int f = (mn >= 0.001f && mn < 1.0f) ? kImgSmall : 0;
   if (!(x - rr > win_lo && x + rr < win_hi)) f |= kImgWide;     // (NaN / inf anywhere: the comparisons fail)
@@ -307,7 +309,7 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
       staged += np;
     };
     // class confidences (:820 conf = obj * cls in the input dtype)
-    float bestv = -__builtin_inff(); int besti = 0x7fffffff;
+    unsigned long long bestk = argmax_key(-__builtin_inff(), 0x7fffffff);
     for (int g = 0; g < ncg; g++) {
       const int c = g * 16 + l16;
       float raw;
@@ -315,11 +317,11 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
       else raw = (cur.valid && c < a.nc) ? ld_as_float<T>(img + (size_t)cur.row * a.no + 5 + c) : 0.f;
       const float v = (cur.valid && c < a.nc) ? mul_in_dtype<T>(raw, cur.obj) : -__builtin_inff();
       if (a.multi_label) stage(cur.valid && c < a.nc && v > thr && class_allowed(a.cm, c), v, c);             // :827, :835
-      else if (c < a.nc && v > bestv) { bestv = v; besti = c; }            // a lane sees ascending c: first max kept
+      else if (c < a.nc) { const unsigned long long kk = argmax_key(v, c); bestk = kk > bestk ? kk : bestk; }   // a NaN wins
     }
     if (!a.multi_label) {
       float bv; int bi;
-      argmax_unkey(row_max_u64(argmax_key(bestv, besti)), bv, bi);                                            // :830
+      argmax_unkey(row_max_u64(bestk), bv, bi);                         // :830 (a NaN maximum fails bv > thr: the row is dropped)
       stage(cur.valid && l16 == 0 && bv > thr && class_allowed(a.cm, bi), bv, bi);                            // :831, :835
     }
   };
@@ -412,7 +414,7 @@ __global__ __launch_bounds__(256) void k_tiny_cross(const float4* __restrict__ c
   __syncthreads();
   for (long long j = tid; j < n; j += 256) {                     // the image's short-sided candidates: every part builds the same set
     const float4 c0 = cand[(base + j) * 2];
-    const float mn = c0.w < c0.z ? c0.w : c0.z;
+    const float mn = min_nan(c0.z, c0.w);
     if (mn >= 0.001f && mn < 1.0f) { const int k = atomicAdd(&s_n, 1); if (k < kTinyMax) s_list[k] = (int)j; }
   }
   __syncthreads();
@@ -432,7 +434,7 @@ __global__ __launch_bounds__(256) void k_tiny_cross(const float4* __restrict__ c
   float* myscr = scr + wv * (RotGeom::SCR * 64) + lane;
   for (long long j = (long long)part * 256 + tid; j < n; j += (long long)gridDim.x * 256) {
     const float4 c0 = cand[(base + j) * 2], c1 = cand[(base + j) * 2 + 1];
-    if (fminf(c0.z, c0.w) < 0.001f) continue;                    // dropped by obb_nms (nms_rotated_wrapper.py:32): never a partner
+    if (box_too_small(c0.z, c0.w)) continue;                      // dropped by obb_nms (nms_rotated_wrapper.py:32): never a partner
     const float offB = c1.z * class_offset;
     const RBoxFeat B = rbox_make_feat(c0.x + offB, c0.y + offB, c0.z, c0.w, c1.x);
     const unsigned long long kB = keys[base + j];
@@ -529,8 +531,7 @@ __global__ void k_prep_cand(const float4* __restrict__ cand, const uint32_t* __r
     RotGeom::pack(f, q);
 #pragma unroll
     for (int k = 0; k < 4; k++) rec[(size_t)p * 4 + k] = q[k];
-    const float mn = (c0.w < c0.z) ? c0.w : c0.z;
-    ok = !(mn < 0.001f);                                         // nms_rotated_wrapper.py:32
+    ok = !box_too_small(c0.z, c0.w);                             // nms_rotated_wrapper.py:32
   }
   const u64 m = __ballot(ok);
   if ((threadIdx.x & 63) == 0 && m) alive[p >> 6] = m;           // the bitmap was zeroed before
@@ -800,8 +801,7 @@ __global__ __launch_bounds__(1024) void k_sort_prep_lds(const float4* __restrict
         RotGeom::pack(f, rq);
 #pragma unroll
         for (int u = 0; u < 4; u++) rec[(size_t)(b0 + p) * 4 + u] = rq[u];
-        const float mn = (c0.w < c0.z) ? c0.w : c0.z;
-        if (!(mn < 0.001f)) atomicOr(&s_abits[p >> 6], 1ull << (p & 63));   // nms_rotated_wrapper.py:32
+        if (!box_too_small(c0.z, c0.w)) atomicOr(&s_abits[p >> 6], 1ull << (p & 63));   // nms_rotated_wrapper.py:32
       }
     }
     __syncthreads();
@@ -849,8 +849,7 @@ __global__ __launch_bounds__(1024) void k_sort_prep_lds(const float4* __restrict
       RotGeom::pack(f, q);
 #pragma unroll
       for (int u = 0; u < 4; u++) rec[(size_t)(b0 + i) * 4 + u] = q[u];
-      const float mn = (c0.w < c0.z) ? c0.w : c0.z;
-      ok = !(mn < 0.001f);                                       // nms_rotated_wrapper.py:32
+      ok = !box_too_small(c0.z, c0.w);                           // nms_rotated_wrapper.py:32
     }
     const u64 bits = __ballot(ok);
     if ((tid & 63) == 0 && i < e64) alive[(size_t)(b0 + i) >> 6] = bits;
@@ -1103,8 +1102,7 @@ struct SmallSelfSort {
         G::pack(f, rq);
 #pragma unroll
         for (int u = 0; u < 4; u++) s_rec[rank * G::RECQ + u] = rq[u];
-        const float mn = (c0.w < c0.z) ? c0.w : c0.z;
-        if (!(mn < 0.001f)) atomicOr(&s_alive[rank >> 6], 1ull << (rank & 63));        // nms_rotated_wrapper.py:32
+        if (!box_too_small(c0.z, c0.w)) atomicOr(&s_alive[rank >> 6], 1ull << (rank & 63));        // nms_rotated_wrapper.py:32
       }
     }
     __syncthreads();                                             // the staged members are read: their place becomes the bit matrix

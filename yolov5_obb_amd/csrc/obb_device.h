@@ -47,4 +47,11 @@ constexpr float f32_floor(double d) {
 static_assert((double)f32_ceil(1e-6) >= 1e-6 && (double)f32_next_down(f32_ceil(1e-6)) < 1e-6, "f32_ceil");
 static_assert((double)f32_floor(1e-14) <= 1e-14 && (double)f32_next_up(f32_floor(1e-14)) > 1e-14, "f32_floor");
 
+// ---- the small-box rule of obb_nms (nms_rotated_wrapper.py:32): too_small = dets[:, [2, 3]].min(1)[0] < 0.001 ----
+// torch.min propagates NaN and NaN < 0.001 is false: a box with a NaN side is never too small, whatever the other side is.
+// (A plain (b < a) ? b : a returns the finite side of (0.0005, NaN) and dropped such a box; fminf ignores the NaN the same way.)
+// Compared in the tensor's dtype: float boxes against 0.001f, double boxes against 0.001.
+template <typename F> OBB_HD F min_nan(F a, F b) { return (a != a || b != b) ? a + b : (b < a ? b : a); }
+template <typename F> OBB_HD bool box_too_small(F w, F h) { return min_nan(w, h) < F(0.001); }
+
 }  // namespace obb
