@@ -364,7 +364,11 @@ size_t obb_loss_workspace_bytes(const obb_loss_config* cfg, int64_t nt);
 
 /* ComputeLoss.build_targets (utils/loss.py:194-275) into the workspace; counts_out[0..nl) (device, int32) receives
  * the number of matched rows per level and counts_out[OBB_LOSS_MAX_LEVELS] a non-zero flag when a target row names
- * an image or class outside the batch (the reference raises IndexError there).  No host synchronisation. */
+ * an image or class outside the batch (the reference raises IndexError there).  No host synchronisation.
+ * Bad target rows: a row that matches some anchor of some level is bad when its image index (truncated like .long()) is
+ * outside [0, bs), its class is negative, or nc > 1 and its class is >= nc.  With nc == 1 the reference never indexes by
+ * class (utils/loss.py:163), so any class >= 0 is accepted and the loss is finite.  Negative image or class indices are
+ * bad for every nc although torch would wrap them.  A bad row makes loss_out[0] and every gradient NaN. */
 int obb_loss_build_targets(const obb_loss_config* cfg, const float* targets, int64_t nt, int64_t tcols, int32_t* counts_out,
                            void* ws, size_t ws_bytes, void* stream);
 /* Rows of one level in the reference's order (offset-major, anchor-major, target order), after the caller has read

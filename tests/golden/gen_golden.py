@@ -183,6 +183,17 @@ def load_reference():
     return ext, G, R, L, M, Y
 
 
+def patch_clamp_():
+    """torch >= 1.11 rejects float-tensor bounds in clamp_ on int64 (utils/loss.py:267): same patch as SURVEY 8c(3),
+    applied from the outside so that no reference code is copied.  Returns the original method (restore it after use)."""
+    _orig_clamp_ = torch.Tensor.clamp_
+    def _clamp_(self, min=None, max=None):
+        cv = lambda v: int(v.item()) if isinstance(v, torch.Tensor) and not self.is_floating_point() else v
+        return _orig_clamp_(self, cv(min), cv(max))
+    torch.Tensor.clamp_ = _clamp_
+    return _orig_clamp_
+
+
 def main():
     oracle.build(with_ref=True)
     ext, G, R, L, M, Y = load_reference()
@@ -321,13 +332,7 @@ def main():
     print("detect decode ok", tuple(z.shape))
 
     # ------------------------------------------------------------------ F. ComputeLoss
-    # torch >= 1.11 rejects float-tensor bounds in clamp_ on int64 (utils/loss.py:267): same patch as SURVEY 8c(3),
-    # applied from the outside so that no reference code is copied.
-    _orig_clamp_ = torch.Tensor.clamp_
-    def _clamp_(self, min=None, max=None):
-        cv = lambda v: int(v.item()) if isinstance(v, torch.Tensor) and not self.is_floating_point() else v
-        return _orig_clamp_(self, cv(min), cv(max))
-    torch.Tensor.clamp_ = _clamp_
+    _orig_clamp_ = patch_clamp_()
 
     class _M(torch.nn.Module):                                       # what ComputeLoss.__init__ reads (utils/loss.py:93-120)
         def __init__(self, nc, hyp):

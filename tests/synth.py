@@ -211,21 +211,54 @@ def scaled_hyp(nc, imgsz=1024, nl=3):
     return h
 
 
-def s_loss(bs, nc, nt, seed=0, imgsz=1024, sizes=None):
-    """S-loss: raw head outputs p[i] ~ N(0,1) at (bs,3,ny,nx,5+nc+180) and nt targets
-    [img, cls, cx, cy, l, s, theta, csl x 180] in pixels (utils/datasets.py:637-659 layout)."""
+P6_ANCHORS = [[19, 27, 44, 40, 38, 94], [96, 68, 86, 152, 180, 137], [140, 301, 303, 264, 238, 542],
+              [436, 615, 739, 380, 925, 792]]                                  # a four-level (P3-P6) head
+P6_STRIDES = [8.0, 16.0, 32.0, 64.0]
+
+
+def head_anchors(nl, na=3):
+    """(anchors, strides) of an nl-level, na-anchor head: anchors (nl, na, 2) in PIXELS as a model yaml lists them, strides
+    8 * 2**i.  nl = 3 / na = 3 is DEFAULT_ANCHORS and nl = 4 / na = 3 is P6_ANCHORS; every other shape gets deterministic
+    anchors that grow with the stride and are never square (so that a swapped l / s ratio changes the match)."""
+    if na == 3 and nl == 3:
+        a, st = DEFAULT_ANCHORS, DEFAULT_STRIDES
+    elif na == 3 and nl == 4:
+        a, st = P6_ANCHORS, P6_STRIDES
+    else:
+        st = [8.0 * 2 ** i for i in range(nl)]
+        a = [[v for k in range(na) for v in (s * (1.25 + 3.0 * (k + 0.5) / na), s * (0.75 + 1.5 * ((3 * k) % na + 0.5) / na))]
+             for s in st]
+    return torch.tensor(a, dtype=torch.float32).view(nl, na, 2), torch.tensor(st, dtype=torch.float32)
+
+
+def s_loss(bs, nc, nt, seed=0, imgsz=1024, sizes=None, na=3, anchors=None):
+    """S-loss: raw head outputs p[i] ~ N(0,1) at (bs,na,ny,nx,5+nc+180) and nt targets
+    [img, cls, cx, cy, l, s, theta, csl x 180] in pixels (utils/datasets.py:637-659 layout).
+
+    sizes: one entry per level, n (a square n x n grid) or an (ny, nx) pair; the targets' centres then cover
+    [0, imgsz) in x and [0, imgsz * ny / nx) in y of level 0.  anchors: optional (nl, na, 2) anchors in pixels; the
+    targets' (l, s) are then drawn around them (a random anchor of a random level times [0.4, 2.5)), so that every level
+    matches some of them.  With the default arguments the result is byte-identical to what it has always been."""
     from oracle import pyref
     g = torch.Generator().manual_seed(seed)
     no = 5 + nc + 180
     sizes = sizes or [int(imgsz / s) for s in DEFAULT_STRIDES]
-    p = [torch.randn(bs, 3, n, n, no, generator=g) for n in sizes]
+    shapes = [(n, n) if isinstance(n, int) else (int(n[0]), int(n[1])) for n in sizes]
+    p = [torch.randn(bs, na, ny, nx, no, generator=g) for ny, nx in shapes]
     t = torch.zeros(nt, 7 + 180)
     if nt:
         t[:, 0] = torch.randint(0, bs, (nt,), generator=g).float()
         t[:, 1] = torch.randint(0, nc, (nt,), generator=g).float()
         t[:, 2:4] = torch.rand(nt, 2, generator=g) * imgsz
-        t[:, 4] = torch.rand(nt, generator=g) * 100 + 20
-        t[:, 5] = torch.rand(nt, generator=g) * 20 + 8
+        if shapes[0][0] != shapes[0][1]:
+            t[:, 3] *= shapes[0][0] / shapes[0][1]
+        if anchors is None:
+            t[:, 4] = torch.rand(nt, generator=g) * 100 + 20
+            t[:, 5] = torch.rand(nt, generator=g) * 20 + 8
+        else:
+            a = torch.as_tensor(anchors, dtype=torch.float32).reshape(-1, 2)
+            pick = torch.randint(0, a.shape[0], (nt,), generator=g)
+            t[:, 4:6] = a[pick] * (torch.rand(nt, 2, generator=g) * 2.1 + 0.4)
         th = (torch.rand(nt, generator=g) - 0.5) * pyref.PI
         t[:, 6] = th
         ang = th.double().numpy() * 180 / pyref.PI + 90

@@ -8,8 +8,7 @@ from tests import synth
 
 pytestmark = pytest.mark.gpu
 
-P6_ANCHORS = [[19, 27, 44, 40, 38, 94], [96, 68, 86, 152, 180, 137], [140, 301, 303, 264, 238, 542], [436, 615, 739, 380, 925, 792]]
-P6_STRIDES = [8.0, 16.0, 32.0, 64.0]
+P6_ANCHORS, P6_STRIDES = synth.P6_ANCHORS, synth.P6_STRIDES
 
 
 @pytest.fixture(params=["compiled", "ctypes"])

@@ -1,8 +1,9 @@
 """GPU parity of the HIP ComputeLoss (yolov5_obb_amd/utils/loss.py -> obb_loss_* in libobb_hip.so) against the CPU
 oracle (oracle/pyref.py: build_targets / compute_loss, pinned to the reference's utils/loss.py by tests/golden).
 
-Tolerances (BASELINE.json north_star: "within 1e-5 on IoU/loss scalars"): loss scalars rtol 1e-5; gradients rtol 1e-4
-of the tensor's max magnitude (hand-written derivatives vs torch autograd, both fp32); build_targets indices bit-exact.
+Tolerances (BASELINE.json north_star: "within 1e-5 on IoU/loss scalars"): loss scalars rtol 1e-5; gradients 1e-5 of the
+largest magnitude of each channel group (box, objectness, class, CSL; hand-written derivatives vs torch autograd, both fp32);
+build_targets indices bit-exact.
 """
 import numpy as np
 import pytest
@@ -10,6 +11,7 @@ import torch
 
 from oracle import pyref
 from tests import synth
+from tests.loss_cases import groups as channel_groups
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +48,29 @@ def run_both(cl, spec, p, t, dev, dtype=torch.float32):
     return (lo, io, pc), (lg, ig, pg)
 
 
-ACHIEVED = {"scalar_rel": 0.0, "grad_rel": 0.0, "tensors": 0}      # reported by test_zz_report_achieved_errors
+GROUPS = ("box", "obj", "cls", "csl")
+# reported by test_zz_report_achieved_errors; tests/test_loss_configs_gpu.py adds its fp32 cases
+ACHIEVED = {"scalar_rel": 0.0, "tensors": 0, **{"grad_" + k: 0.0 for k in GROUPS}}
+
+
+def check_grads(pg, pc, grtol=1e-5, atol=0.0):
+    """Every element of every gradient tensor against the oracle's, per channel group: the class gradients are scaled by
+    1 / (n * nc) and the CSL gradients by 1 / (n * 180), orders of magnitude below the box and objectness gradients, so each
+    group's error is measured against that group's own largest |gradient|.  A group whose oracle gradient is all zero (no
+    matched row on the level, or the class term at nc = 1) must be exactly zero.  A NaN anywhere fails."""
+    for a, b in zip(pg, pc):
+        nc = b.shape[-1] - 185
+        ga, gb = a.grad.float().cpu(), b.grad
+        assert ga.shape == gb.shape
+        for name, sl in channel_groups(nc).items():
+            x, y = ga[..., sl], gb[..., sl]
+            scale = y.abs().max().item() if y.numel() else 0.0
+            err = (x - y).abs().max().item() if y.numel() else 0.0
+            if a.dtype == torch.float32 and b.dtype == torch.float32 and scale > 0:
+                ACHIEVED["grad_" + name] = max(ACHIEVED["grad_" + name], err / scale)
+            assert err <= grtol * scale + atol, (name, tuple(a.shape), err, scale)
+        if a.dtype == torch.float32:
+            ACHIEVED["tensors"] += 1
 
 
 def check(o, g, rtol=1e-5, grtol=1e-5):
@@ -60,14 +84,7 @@ def check(o, g, rtol=1e-5, grtol=1e-5):
     ok = np.abs(ref) > 1e-3
     if ok.any():
         ACHIEVED["scalar_rel"] = max(ACHIEVED["scalar_rel"], float(np.max(np.abs(got[ok] - ref[ok]) / np.abs(ref[ok]))))
-    for a, b in zip(pg, pc):
-        ga, gb = a.grad.float().cpu(), b.grad
-        scale = gb.abs().max().item() + 1e-12
-        err = (ga - gb).abs().max().item()
-        assert err <= grtol * scale, (err, scale)
-        if b.dtype == torch.float32 and a.dtype == torch.float32:
-            ACHIEVED["grad_rel"] = max(ACHIEVED["grad_rel"], err / scale)
-            ACHIEVED["tensors"] += 1
+    check_grads(pg, pc, grtol)
 
 
 @pytest.mark.parametrize("nt", [0, 1, 50, 400])
@@ -149,6 +166,10 @@ def test_sort_obj_iou(dev):
     lo, io = pyref.compute_loss(spec, pc, t.clone(), sort_obj_iou=True)
     assert np.allclose(loss.detach().cpu().numpy(), lo.detach().numpy(), rtol=1e-5, atol=1e-6)
     assert np.allclose(items.cpu().numpy(), io.numpy(), rtol=1e-5, atol=1e-6)
+    # the gradients too: the winner of each crowded cell (k_loss_entries_bwd's tie rule) sets its objectness target
+    loss.backward()
+    lo.backward()
+    check((lo, io, pc), (loss, items, pg))
 
 
 def test_fp16_heads(dev):
@@ -163,6 +184,7 @@ def test_fp16_heads(dev):
         assert a.grad.dtype == torch.float16
         scale = b.grad.abs().max().item()
         assert (a.grad.float().cpu() - b.grad).abs().max().item() <= 2e-3 * scale + 1e-7
+    check_grads(pg, pc, grtol=2e-3, atol=1e-7)                  # and per channel group
 
 
 def test_grad_scale_and_full_size(dev):
@@ -281,8 +303,13 @@ def test_autobalance_three_steps(dev, oracle_lib):
 
 
 def test_zz_report_achieved_errors(dev):
-    """Not a check of its own: prints what the fp32 comparisons above achieved (pytest shows it in the warnings summary).  The
-    asserted tolerances are 1e-5 relative on the loss scalars (north_star) and 1e-5 of the tensor's largest |gradient| (1e-4 until the achieved figure was printed: 3.3e-7)."""
+    """Not a check of its own: prints what the fp32 comparisons above (and those of tests/test_loss_configs_gpu.py, which
+    runs first) achieved; pytest shows it in the warnings summary.  The asserted tolerances are 1e-5 relative on the loss
+    scalars (north_star) and, per channel group (box, objectness, class, CSL), 1e-5 of that group's largest |gradient|.  The
+    earlier rule, 1e-5 of the whole tensor's largest |gradient|, allowed the class and CSL groups errors up to their own size.
+    Measured on the MI355X over both modules: box 6.6e-7, objectness 2.3e-6, class 2.3e-6, CSL 4.4e-6 (every group meets 1e-5)."""
     import warnings
     warnings.warn(UserWarning(f"ComputeLoss vs oracle (fp32 cases of this run): loss scalars max rel. error {ACHIEVED['scalar_rel']:.2e}; "
-                              f"gradients max |err| / max |grad| = {ACHIEVED['grad_rel']:.2e} over {ACHIEVED['tensors']} tensors"))
+                              "gradients max |err| / max |grad| of the group: " +
+                              ", ".join(f"{k} {ACHIEVED['grad_' + k]:.2e}" for k in GROUPS) +
+                              f" over {ACHIEVED['tensors']} tensors"))

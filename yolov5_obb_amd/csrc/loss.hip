@@ -129,7 +129,9 @@ __device__ __forceinline__ BtCand bt_eval(const LossDev& d, int lv, long long id
   if (ok) {
     c.b = (int)tr[0];                                                                  // :256  .long() truncates
     const int cls = (int)tr[1];
-    if (c.b < 0 || c.b >= d.bs || cls < 0 || cls >= d.nc) { ok = false; c.bad = true; }   // the reference raises IndexError
+    // the reference raises IndexError on b >= bs (:140) and, with nc > 1 only, on cls >= nc (:165); with nc == 1 it never
+    // indexes by class.  Negative indices, which torch wraps, are flagged too (include/obb_hip.h)
+    if (c.b < 0 || c.b >= d.bs || cls < 0 || (d.nc > 1 && cls >= d.nc)) { ok = false; c.bad = true; }
   }
   c.ok = ok;
   return c;

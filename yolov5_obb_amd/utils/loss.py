@@ -198,8 +198,9 @@ class ComputeLoss:
                 _lib.check(L.obb_loss_build_targets(C.byref(cfg), _lib.ptr(tg), nt, tcols, _lib.ptr(counts), _lib.ptr(ws),
                                                     ws.numel(), _lib.stream_ptr(dev)), "obb_loss_build_targets")
             cnt = counts.tolist()
-            if cnt[_MAX_LV]:
-                raise IndexError("build_targets: a target row names an image or class outside the batch")
+            if cnt[_MAX_LV]:      # the device flag: b outside [0, bs), a negative class, or cls >= nc when nc > 1
+                raise IndexError("build_targets: a matched target row names an image outside the batch, a negative class, "
+                                 "or (nc > 1) a class >= nc")
             for i in range(self.nl):
                 n = cnt[i]
                 idx = torch.empty((n, 4), dtype=torch.int64, device=dev)
