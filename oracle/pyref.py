@@ -318,15 +318,43 @@ def box_iou(box1, box2):
     return inter / (area1[:, None] + area2 - inter)
 
 
-def process_batch(detections, labels, iouv):
-    """val.py:69-90, numpy steps included (argsort()[::-1], two np.unique(return_index=True))."""
+def val_label_boxes(targets_img, gain, pad, shape_hw, dtype=torch.float32):
+    """val.py:238-243 with scale_coords / clip_coords (utils/general.py:621-633): the labels of ONE image, rows
+    [img cls cx cy l s theta ...] in the letterboxed frame -> labels_hbbn (m, 5) [cls x1 y1 x2 y2] in the native frame.
+    rbox2poly -> poly2hbb -> xywh2xyxy, then subtract the pad (pad_x, pad_y), divide by the gain, clip to shape_hw = (h, w)."""
+    t = targets_img.to(dtype)
+    tbox = xywh2xyxy(poly2hbb(rbox2poly(t[:, 2:7])))
+    tbox[:, [0, 2]] -= pad[0]
+    tbox[:, [1, 3]] -= pad[1]
+    tbox[:, :4] /= gain
+    tbox[:, [0, 2]] = tbox[:, [0, 2]].clamp(0, shape_hw[1])
+    tbox[:, [1, 3]] = tbox[:, [1, 3]].clamp(0, shape_hw[0])
+    return torch.cat((t[:, 1:2], tbox), 1)
+
+
+def process_batch(detections, labels, iouv, ties=None):
+    """val.py:69-90, numpy steps included (argsort()[::-1], two np.unique(return_index=True)).
+
+    ties=None: the reference as written.  Its descending order is `argsort()[::-1]` with numpy's default sort, which is not
+    stable: when two matches have EXACTLY the same IoU (duplicate ground-truth boxes do that) which of them np.unique meets
+    first -- and with it which label a detection keeps and which detection a label keeps -- depends on numpy's sort
+    implementation and on the number of matches.  On tie-free input the result is unique.
+    ties="first": pinned rule, one legal order of that unstable sort: a stable sort of the negated IoU, so that among equal IoUs
+    the match that comes first in torch.where's (label, detection) row-major order stays first.  A detection then keeps the
+    FIRST label (in label order) among its maxima, and a label the LOWEST-indexed detection that kept it -- the rule of the
+    kernels (csrc/head.hip: k_pb_best, k_vt_dets, k_vt_stats).  Made explicit here so that the oracle does not depend on
+    numpy's sort, like the `tobj` rule in compute_loss."""
+    assert ties in (None, "first")
     correct = torch.zeros(detections.shape[0], iouv.shape[0], dtype=torch.bool)
     iou = box_iou(labels[:, 1:], detections[:, :4])
     x = torch.where((iou >= iouv[0]) & (labels[:, 0:1] == detections[:, 5]))
     if x[0].shape[0]:
         matches = torch.cat((torch.stack(x, 1), iou[x[0], x[1]][:, None]), 1).numpy()
         if x[0].shape[0] > 1:
-            matches = matches[matches[:, 2].argsort()[::-1]]
+            if ties == "first":
+                matches = matches[np.argsort(-matches[:, 2], kind='stable')]
+            else:
+                matches = matches[matches[:, 2].argsort()[::-1]]
             matches = matches[np.unique(matches[:, 1], return_index=True)[1]]
             matches = matches[np.unique(matches[:, 0], return_index=True)[1]]
         matches = torch.Tensor(matches)
