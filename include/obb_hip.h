@@ -471,7 +471,8 @@ int obb_process_batch_f32(const float* det6, int64_t n, const float* lab5, int64
 /* out[i] = IoU(a5[i], b5[i]); the device function behind the NMS
  * (single_box_iou_rotated<float>, utils/nms_rotated/src/box_iou_rotated_utils.h:333-360). */
 int obb_rotated_iou_pairs_f32(const float* a5, const float* b5, int64_t n, float* out, void* stream);
-/* out[i*k + j] = IoU(a5[i], b5[j]) */
+/* out[i*k + j] = IoU(a5[i], b5[j]).  One workgroup per 64 x 64 tile, the row tiles on the grid's y axis: n <= 65535 * 64 =
+ * 4,194,240 rows (k is not limited by the grid); a larger n returns OBB_ERR_BAD_ARG and launches nothing -- split the rows. */
 int obb_rotated_iou_matrix_f32(const float* a5, int64_t n, const float* b5, int64_t k, float* out, void* stream);
 /* out[i*k + j] = quad IoU of rows (first 8 floats used) -- devPolyIoU, utils/nms_rotated/src/poly_nms_cuda.cu:122-142.
  * Entries the two proved cone rules of csrc/piou_device.h vouch for are written as the exact +0 the clip would return. */

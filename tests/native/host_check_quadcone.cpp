@@ -1,9 +1,11 @@
 // The exact skip rule of the quad IoU (piou_device.h: quad_cone_bits / quad_cone_skip): whenever the rule
 // fires, the reference's 16-term sum must be EXACTLY +0 and the IoU +0.  Pairs are generated to sit ON the rule's edges:
 // angular gaps from the smallest the fixed-point cones can resolve, spans up to pi, vertices at the minimum distance from the
-// origin, coordinates from 2 to 10^7, slivers, bow ties, clockwise rings, edges along rays, all quadrants and the wrap at the
-// negative x axis.  Compiled twice by tests/test_host_geometry.py: without and WITH FMA contraction (nvcc's default for the
-// reference): the statement holds either way.
+// origin, coordinates from 2 to 10^37 (across the rule's coordinate bound kConeMaxCoord = 2^62: beyond it the products of
+// the clip overflow, the reference returns NaN and the rule must stay silent), slivers, bow ties, clockwise rings, edges along
+// rays, all quadrants and the wrap at the negative x axis; plus fixed pairs of huge rectangles that an ungated rule gets wrong.
+// Compiled twice by tests/test_host_geometry.py: without and WITH FMA contraction (nvcc's default for the reference): the
+// statement holds either way.
 //   usage: host_check_quadcone <n_pairs> <seed>
 #include <cstdio>
 #include <cstdlib>
@@ -131,12 +133,41 @@ int main(int argc, char** argv) {
   const long n = argc > 1 ? atol(argv[1]) : 4000000;
   g.seed(argc > 2 ? (unsigned)atol(argv[2]) : 0u);
   const bool rule2 = argc > 3 ? atol(argv[3]) != 0 : true;      // the second rule's contract is "no FMA contraction": the FMA build passes 0
-  long fired = 0, wrong = 0, near_edge = 0, fired2 = 0, wrong2 = 0, near_edge2 = 0;
+  long fired = 0, wrong = 0, near_edge = 0, fired2 = 0, wrong2 = 0, near_edge2 = 0, fixed_fired = 0;
   float s0[10], s1[10], s2[10], s3[10];
-  static const float kScale[8] = {2.f, 10.f, 300.f, 1024.f, 5000.f, 70000.f, 1e6f, 1e7f};
+  // 2e18 / 4e18: coordinates up to twice the scale, on either side of kConeMaxCoord = 4.6e18
+  // (an odd count: every scale meets every gap of kGap, which cycles with i / 8)
+  constexpr int kNScale = 15;
+  static const float kScale[kNScale] = {2.f, 10.f, 300.f, 1024.f, 5000.f, 70000.f, 1e6f, 1e7f, 1e12f, 2e18f, 4e18f, 1e19f, 1e25f, 1e30f, 1e37f};
   static const float kGap[8] = {1e-4f, 2e-4f, 3e-4f, 5e-4f, 1e-3f, 1e-2f, 0.3f, 1.5f};
+  // Fixed cases: P = an axis-aligned square of side 0.05 s centred at (s, 0.1 s), Q = the same at (0.1 s, s) -- Q counter-clockwise
+  // of P by 78 degrees -- and an ordinary 5 x 5 box at (100, 10) against the huge Q.  From s = 1e25 on the reference's products
+  // overflow and its IoU is NaN; s = 1e18 lies inside the bound, where the rule fires and the IoU is +0.
+  {
+    static const float kHuge[5] = {1e18f, 3e19f, 1e25f, 1e30f, 1e37f};
+    auto square = [](float cx, float cy, float side, float* q) {
+      const float h = side / 2;
+      q[0] = cx - h; q[1] = cy - h; q[2] = cx + h; q[3] = cy - h; q[4] = cx + h; q[5] = cy + h; q[6] = cx - h; q[7] = cy + h;
+    };
+    for (int c = 0; c < 10; c++) {
+      const float s = kHuge[c / 2];
+      float p[8], q[8];
+      if (c % 2) square(100.f, 10.f, 5.f, p); else square(s, 0.1f * s, 0.05f * s, p);
+      square(0.1f * s, s, 0.05f * s, q);
+      const obb::QuadFeat P = obb::quad_make_feat(p), Q = obb::quad_make_feat(q);
+      for (int role = 0; role < 2; role++) {
+        const obb::QuadFeat& A = role ? Q : P; const obb::QuadFeat& B = role ? P : Q;
+        const bool r1 = obb::quad_cone_skip(obb::quad_cone_bits(A), obb::quad_cone_bits(B)), r2 = rule2 && rule2_fires(A, B);
+        if (!r1 && !r2) continue;
+        fixed_fired++;
+        const float v = obb::quad_iou<1>(A, B, s0, s1, s2, s3);
+        uint32_t vb; memcpy(&vb, &v, 4);
+        if (vb != 0u) { (r1 ? wrong : wrong2)++; fprintf(stderr, "counter-example (fixed pair, s = %g, %s P): iou bits %08x\n", s, c % 2 ? "small" : "huge", vb); }
+      }
+    }
+  }
   for (long i = 0; i < n; i++) {
-    const float scale = kScale[i % 8];
+    const float scale = kScale[i % kNScale];
     const float base = (U() - 0.5f) * 6.2831853f;                 // anywhere, incl. across the negative x axis
     const float wp = U() < 0.5f ? U() * 0.02f : U() * 1.2f, wq = U() < 0.5f ? U() * 0.02f : U() * 1.2f;
     const float gap = kGap[(i / 8) % 8] * (0.5f + U());
@@ -179,6 +210,6 @@ int main(int argc, char** argv) {
     if (vb != 0u) { wrong2++; if (wrong2 < 5) fprintf(stderr, "counter-example (rule 2, family %ld): iou bits %08x\n", i % 4, vb); }
   }
   printf("family2_fired=%ld,%ld,%ld,%ld at_edge2=%ld tier1=%ld tier2=%ld ", fam_fired[0], fam_fired[1], fam_fired[2], fam_fired[3], edge2, g_tier[1], g_tier[2]);
-  printf("pairs=%ld fired=%ld near_edge=%ld wrong=%ld fired2=%ld near_edge2=%ld wrong2=%ld\n", n, fired, near_edge, wrong, fired2, near_edge2, wrong2);
+  printf("pairs=%ld fixed_fired=%ld fired=%ld near_edge=%ld wrong=%ld fired2=%ld near_edge2=%ld wrong2=%ld\n", n, fixed_fired, fired, near_edge, wrong, fired2, near_edge2, wrong2);
   return (wrong || wrong2) ? 1 : 0;
 }

@@ -27,10 +27,10 @@ def test_voc_eval_equals_the_reference_devkit(dev, oracle_lib, tmp_path, name):
     assert mean_ap == sum(aps) / 2 and np.array_equal(classaps, 100 * np.array(aps))
 
 
-def test_best_gt_vs_oracle_per_detection(dev, oracle_lib):
-    """Images with 0 .. 900 ground-truth quads (several 64-lane rounds), exact duplicates (ties -> first index), degenerate
-    quads (NaN -> first NaN), detections far from everything (-inf, -1)."""
-    from yolov5_obb_amd.DOTA_devkit.dota_evaluation_task1 import best_gt
+def best_gt_inputs():
+    """(dets, dimg, gts, off) of test_best_gt_vs_oracle_per_detection: images with 0 .. 900 ground-truth quads (several 64-lane
+    rounds), exact duplicates, degenerate quads, detections far from everything; the detections in shuffled order.  Seeded: every
+    call returns the same arrays (tests/test_pairwise_edges_gpu.py cycles them past one grid pass of k_eval_best_gt)."""
     rng = np.random.RandomState(3)
 
     def quads(n, extent):
@@ -59,7 +59,14 @@ def test_best_gt_vs_oracle_per_detection(dev, oracle_lib):
         dets.append(d); dimg += [im] * nd
     gts, dets, dimg = np.concatenate(gts), np.concatenate(dets), np.array(dimg, dtype=np.int32)
     perm = rng.permutation(len(dets))
-    dets, dimg = dets[perm], dimg[perm]
+    return dets[perm], dimg[perm], gts, off
+
+
+def test_best_gt_vs_oracle_per_detection(dev, oracle_lib):
+    """Images with 0 .. 900 ground-truth quads (several 64-lane rounds), exact duplicates (ties -> first index), degenerate
+    quads (NaN -> first NaN), detections far from everything (-inf, -1)."""
+    from yolov5_obb_amd.DOTA_devkit.dota_evaluation_task1 import best_gt
+    dets, dimg, gts, off = best_gt_inputs()
     ov, jm = best_gt(dets, dimg, gts, np.array(off))
     n_nan = n_none = 0
     for d in range(len(dets)):

@@ -59,8 +59,9 @@ def test_quad_cone_rule_gives_exactly_zero(tmp_path, fma):
     """The PROVED skip rule of the quad IoU (piou_device.h quad_cone_skip): whenever the second quad's cone
     lies counter-clockwise of the first's, every one of the 16 terms of the reference's sum is exactly zero and the IoU is
     +0 -- checked on pairs generated to sit on the rule's edges (smallest resolvable gaps, spans up to pi, vertices at the minimum
-    distance, coordinates 2 .. 1e7, bow ties, clockwise rings), in a build without and in a build WITH FMA contraction
-    (nvcc's default for the reference's .cu files).
+    distance, coordinates 2 .. 1e37 across the rule's coordinate bound 2^62, bow ties, clockwise rings, and fixed pairs of huge
+    squares on which the reference returns NaN: the rule fires on the one inside the bound only), in a build without and in a
+    build WITH FMA contraction (nvcc's default for the reference's .cu files).
     Round 6: the SECOND proved rule (quad_cone2_skip / quad_cone2_nofuzzy: the first quad counter-clockwise of the second; tier 1
     on the extended-edge cone, tier 2 on the plain cone plus the pair check) in the build without contraction -- this project's
     arithmetic contract, the one the rule is stated for -- on the same pairs and on four families of its own: rectangles with
@@ -75,6 +76,7 @@ def test_quad_cone_rule_gives_exactly_zero(tmp_path, fma):
     assert r.returncode == 0 and " wrong=0" in r.stdout and " wrong2=0" in r.stdout, r.stdout + r.stderr
     vals = dict(kv.split("=") for kv in r.stdout.split())
     assert int(vals["fired"]) > 1500000 and int(vals["near_edge"]) > 500000, r.stdout
+    assert int(vals["fixed_fired"]) == 2, r.stdout            # s = 1e18 (huge P, small P); never from s = 3e19 on
     if not fma:
         assert int(vals["fired2"]) > 1000000 and int(vals["tier1"]) > 300000 and int(vals["tier2"]) > 300000, r.stdout
         assert int(vals["at_edge2"]) > 200000 and min(int(v) for v in vals["family2_fired"].split(",")) > 30000, r.stdout

@@ -15,6 +15,9 @@ def poly_overlaps(boxes, query_boxes, device_id=0):
     query_boxes = np.ascontiguousarray(query_boxes, dtype=np.float32)
     if boxes.ndim != 2 or query_boxes.ndim != 2:
         raise ValueError("Buffer has wrong number of dimensions (expected 2)")   # Cython's buffer check
+    if boxes.shape[1] != 5 or query_boxes.shape[1] != 5:
+        # `_overlaps` reads rows of five floats from a bare pointer (poly_overlaps.hpp:1): a wider array would be misread
+        raise ValueError(f"poly_overlaps: (N,5) and (K,5) expected, got {boxes.shape} and {query_boxes.shape}")
     n, k = boxes.shape[0], query_boxes.shape[0]
     overlaps = np.zeros((n, k), dtype=np.float32)
     if n and k:

@@ -162,6 +162,7 @@ __global__ __launch_bounds__(64) void k_quad_strip(const float* __restrict__ a, 
 }
 
 // units of 16 rows x chunk columns, chunk a multiple of 64 chosen for >= ~3 units per wave slot of the device (256 CUs x 14)
+// (chunk > 64 needs ~22 M pairs: tests/test_pairwise_edges_gpu.py::test_quad_strip_multi_tile_chunks mirrors this formula)
 static int quad_strip_launch(bool devkit, const float* a, long long sa, long long n, const float* b, long long sb, long long k, float* out,
                              hipStream_t st) {
   const long long strips = (n + kQsRows - 1) / kQsRows;

@@ -243,7 +243,8 @@ OBB_HD float f16_bits_to_float(uint32_t h) {
 }
 
 // ---- the exact rule: the second quad's cone lies counter-clockwise of the first's ------------------------------------
-// PROVED, at any coordinate magnitude (DESIGN.md section 4.1 spells the argument out).  quad_iou(P, Q) clips every triangle
+// PROVED for coordinates |x|, |y| <= kConeMaxCoord = 2^62 (DESIGN.md section 4.3 spells the argument out; the bound is what keeps
+// the reference's own arithmetic finite, see below).  quad_iou(P, Q) clips every triangle
 // (o, a, b) of P -- o the coordinate origin, (a, b) an edge of P -- first against the line o -> c, c a vertex of Q, with
 //     s(v) = fl(fl(cx * vy) - fl(vx * cy))          (ptri with the origin as the line's first point: no subtraction rounds)
 // and keeps what lies to its LEFT (s > 1e-8).  If every vertex of P lies CLOCKWISE of every vertex of Q as seen from the
@@ -255,16 +256,26 @@ OBB_HD float f16_bits_to_float(uint32_t h) {
 // counter-clockwise of Q the last clip line runs d -> o and the intermediate polygon is not a point: no such statement, and
 // none is used.)  The cone of a quad = the polar angles of its four vertices, as 16-bit fixed point (2 pi / 65536 per unit)
 // widened by two units on either side, which also covers atan2f's error on any libm; a quad around the origin, across the
-// negative x axis, with a vertex within 1.5 (L1) of the origin, with a non-finite coordinate or with zero computed area has no
-// cone and is never skipped by this rule.
+// negative x axis, with a vertex within 1.5 (L1) of the origin, with a coordinate that is not finite or lies beyond
+// kConeMaxCoord, or with zero computed area has no cone and is never skipped by this rule.
+// The coordinate bound: "exactly 0" above needs every intermediate of the reference FINITE -- 0 * inf and inf - inf are NaN, and
+// the reference then returns NaN, not +0 (two 0.05 s squares at (s, 0.1 s) and (0.1 s, s), s >= 1e25; tests/native/
+// host_check_quadcone.cpp).  With all eight coordinates of BOTH quads <= B = 2^62 in magnitude: a product of two coordinates or
+// of a coordinate and an edge vector (<= 2 B) is <= 2^125, every s(.) -- a difference of two such products, fused or not -- is
+// <= 2^126, the ring areas (eight products of <= 2^124, halved) are <= 2^126 each and their sum <= 2^127: all below
+// FLT_MAX ~ 2^128, so the crossings are (+-0 - +-0) / s with s finite and non-zero, the later clips see only the point (0, 0),
+// and the union is finite and non-zero.  Small magnitudes need no bound: no vertex is closer than 1 to the origin.  The gate is
+// per quad, so a pair with ONE huge quad (an ordinary box against the huge square above: NaN as well) is never skipped either.
 constexpr uint32_t kConeNone = 0x0000FFFFu;            // lo = 0xFFFF > hi = 0
+constexpr float kConeMaxCoord = 4611686018427387904.f;   // 2^62
 OBB_HD uint32_t quad_cone_bits(const QuadFeat& q) {
   float lo = 4.f, hi = -4.f;
   bool ok = quad_signed_area(q.x, q.y) != 0.f;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     const float x = q.x[i], y = q.y[i];
-    ok = ok && (x - x == 0.f) && (y - y == 0.f) && (fabsf(x) + fabsf(y) >= 1.5f);
+    // (the bound takes the place of the finiteness test x - x == 0: false for NaN and +-inf as well)
+    ok = ok && (fabsf(x) <= kConeMaxCoord) && (fabsf(y) <= kConeMaxCoord) && (fabsf(x) + fabsf(y) >= 1.5f);
     const float t = atan2f(y, x);
     lo = fminf(lo, t); hi = fmaxf(hi, t);
   }

@@ -55,6 +55,8 @@ def quad_iou_matrix(a, b):
 
 def rbox_overlaps(boxes, query):
     boxes, query = _prep(boxes, "boxes", 5), _prep(query, "query", 5)
+    if boxes.shape[1] != 5 or query.shape[1] != 5:          # the C entry has no row stride
+        raise RuntimeError("rbox_overlaps: (N,5) x (K,5) expected")
     out = torch.empty(boxes.shape[0], query.shape[0], dtype=torch.float32, device=boxes.device)
     with torch.cuda.device(boxes.device):
         rc = _lib.lib().obb_rbox_overlaps_f32(_lib.ptr(boxes), boxes.shape[0], _lib.ptr(query), query.shape[0], _lib.ptr(out),
