@@ -2,7 +2,6 @@
 (oracle/pyref.py) run on the very tensor Detect produced.  fp32: exact rows; fp16: rows compared as canonical sets."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 from oracle import pyref
 from tests import synth
@@ -33,7 +32,7 @@ for dtype in ((torch.float16,) if os.environ.get("PRELUDE", "0") == "1" else (to
     n_got, n_ref = sum(o.shape[0] for o in got), sum(r.shape[0] for r in ref)
     for b in range(bs):
         g, g2, r = got[b].cpu(), got2[b].cpu(), torch.as_tensor(ref[b])
-        same = g.shape == r.shape and (torch.equal(g, r) if dtype == torch.float32 else np.array_equal(synth.canon_rows(g), synth.canon_rows(r)))
+        same = g.shape == r.shape and torch.equal(g, r)
         if not same or not torch.equal(g, g2):
             bad += 1
             print(f"  {dtype} image {b}: gpu {tuple(g.shape)} plain-path {tuple(g2.shape)} oracle {tuple(r.shape)}", flush=True)
