@@ -466,6 +466,26 @@ size_t obb_process_batch_workspace_bytes(int64_t n, int64_t m);
 int obb_process_batch_f32(const float* det6, int64_t n, const float* lab5, int64_t m, const float* iouv, int niou, uint8_t* correct,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ap_per_class (utils/metrics.py:21-114, compute_ap method 'interp') over statistics that stay on the device.  stats = n rows
+ * [correct x niou as 0 / 1, conf, cls] with row_stride >= niou + 2 floats -- the rows obb_val_tail_batch_f32 writes; target_cls =
+ * the class of every label (m floats).  Class ids are integers 0 .. nc_max - 1, nc_max <= 256; 1 <= niou <= 16; n, m < 2^31 - 1.
+ * ORDER: conf descending, ties by ascending row index (np.argsort(-conf, kind='stable')) -- this library's rule: the
+ * reference's order among ties is whatever numpy's introsort leaves.  All arithmetic is double, in numpy's operation order.
+ * Outputs (device), dense by class id -- the host keeps the classes with counts[0][c] > 0 (np.unique(target_cls)):
+ *   ap      [nc_max][niou]
+ *   prf     [nc_max][5]        p, r, f1, tp, fp at the best F1 index
+ *   counts  [2][nc_max]        labels per class, predictions per class
+ *   info    [4]                best F1 index (first argmax of the class-mean F1 over px), true positives at IoU column 0,
+ *                              1 when a class value of either array is not an integer in [0, nc_max), 1 when a conf is NaN
+ *                              (the results are then unspecified)
+ *   curves  [3][nc_max][1000]  p, r, f1 over px = linspace(0, 1, 1000); may be NULL
+ * A class with labels and no predictions keeps zero rows; a predicted class without labels is ignored.  Stream-ordered, no
+ * synchronisation; the argument checks answer before any device call.  The workspace is linear in n. */
+size_t obb_ap_per_class_workspace_bytes(int64_t n, int niou, int nc_max);
+int obb_ap_per_class_f32(const float* stats, int64_t row_stride, int64_t n, int niou, const float* target_cls, int64_t m, int nc_max,
+                         double* ap, double* prf, int32_t* counts, int32_t* info, double* curves, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* ------------------------------------------------------------------ pairwise IoU --------------------- */
 
 /* out[i] = IoU(a5[i], b5[i]); the device function behind the NMS

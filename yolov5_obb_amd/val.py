@@ -83,6 +83,33 @@ def _as_f32_cuda(t, dev):
     return t.to(device=dev, dtype=torch.float32).contiguous()
 
 
+def _pack_dets(preds, dev, n):
+    """The detections of a batch as ONE (n, 7) float32 array (None when n = 0): the split views of
+    non_max_suppression_obb's packed buffer in order, else a copy."""
+    packed, first = None, None
+    ok = True
+    for p in preds:
+        if p.shape[0] == 0:
+            continue
+        if p.device != dev or p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 7 or not p.is_contiguous():
+            if p.device.type != "cuda":
+                _lib.require_cuda(p, "pred")
+            ok = False
+            break
+        if first is None:
+            first, nxt = p, p.data_ptr()
+        if p.data_ptr() != nxt:
+            ok = False
+            break
+        nxt += p.shape[0] * 28
+    if n:
+        if ok and first is not None:
+            packed = first if first.shape[0] == n else torch.as_strided(first, (n, 7), (7, 1))
+        else:
+            packed = torch.cat([p.to(torch.float32) for p in preds], 0).contiguous()
+    return packed
+
+
 def val_tail_batch(preds, targets, shapes, iouv, want_boxes=False):
     """The tail of val.py:209-250 for ALL images of a batch: two launches, and the statistics land in pinned host memory
     that this thread polls (no copy kernel, no blocked stream wait; the host side of this function is most of its time, so it
@@ -111,28 +138,7 @@ def val_tail_batch(preds, targets, shapes, iouv, want_boxes=False):
         offs[b + 1] = offs[b] + counts[b]
     n = offs[bs]
     niou = iouv.shape[0]
-    # the detections as ONE (n, 7) array: the split views of non_max_suppression_obb's packed buffer in order, else a copy
-    packed, first = None, None
-    ok = True
-    for p in preds:
-        if p.shape[0] == 0:
-            continue
-        if p.device != dev or p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 7 or not p.is_contiguous():
-            if p.device.type != "cuda":
-                _lib.require_cuda(p, "pred")
-            ok = False
-            break
-        if first is None:
-            first, nxt = p, p.data_ptr()
-        if p.data_ptr() != nxt:
-            ok = False
-            break
-        nxt += p.shape[0] * 28
-    if n:
-        if ok and first is not None:
-            packed = first if first.shape[0] == n else torch.as_strided(first, (n, 7), (7, 1))
-        else:
-            packed = torch.cat([p.to(torch.float32) for p in preds], 0).contiguous()
+    packed = _pack_dets(preds, dev, n)
     tg = _as_f32_cuda(targets, dev) if targets.dim() == 2 and targets.shape[0] else None
     nt, tcols = (tg.shape[0], tg.shape[1]) if tg is not None else (0, 0)
     iv = _as_f32_cuda(iouv, dev)
@@ -195,3 +201,127 @@ def val_tail_batch(preds, targets, shapes, iouv, want_boxes=False):
     pcls = host[:, niou + 1].split(counts)
     out = list(zip(correct, conf, pcls))
     return (out, (boxes, offs)) if want_boxes else out
+
+
+class ValStats:
+    """The statistics of a whole validation run in DEVICE memory: what val.py:250 appends per image and :269 concatenates, as
+    one (n, niou + 2) array of rows [correct x niou as 0 / 1, conf, cls] (the rows obb_val_tail_batch_f32 writes, in the order
+    of the images) plus the class of every label -- the inputs of utils.metrics.ap_per_class, which then runs on them where
+    they lie.  Nothing is copied to the host and nothing waits for the stream until ap_per_class() / cpu() is called."""
+
+    def __init__(self, niou=10, device=None, capacity=1 << 16):
+        self.niou = int(niou)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("ValStats: device must be a CUDA/HIP device (no CPU path, by design)")
+        self.n, self.m = 0, 0
+        self._rows = torch.empty((max(1, int(capacity)), self.niou + 2), dtype=torch.float32, device=self.device)
+        self._tcls = torch.empty(max(1, int(capacity) // 8), dtype=torch.float32, device=self.device)
+        self._result = None
+
+    @property
+    def rows(self):
+        """(n, niou + 2) float32 on the device."""
+        return self._rows[:self.n]
+
+    @property
+    def target_cls(self):
+        """(m) float32 on the device: the class of every label seen, images without detections included (val.py:213-215)."""
+        return self._tcls[:self.m]
+
+    @staticmethod
+    def _grown(buf, used, need):
+        """buf with room for `need` leading entries (grown geometrically; the first `used` are kept)."""
+        if need <= buf.shape[0]:
+            return buf
+        new = torch.empty((max(need, 2 * buf.shape[0]),) + tuple(buf.shape[1:]), dtype=buf.dtype, device=buf.device)
+        new[:used] = buf[:used]
+        return new
+
+    def add_batch(self, preds, targets, shapes, iouv, want_boxes=False):
+        """The inputs of val_tail_batch; the rows go straight behind the ones already held.  Returns None, or with want_boxes
+        the packed device arrays (pred_poly, pred_hbb, pred_polyn, pred_hbbn) and the per-image offsets."""
+        import ctypes as C
+        dev = self.device
+        bs = len(preds)
+        if int(iouv.shape[0]) != self.niou:
+            raise RuntimeError(f"ValStats: iouv has {int(iouv.shape[0])} levels, this accumulator {self.niou}")
+        offs = [0] * (bs + 1)
+        for b in range(bs):
+            if preds[b].device != dev:
+                _lib.require_cuda(preds[b], "pred")
+                raise RuntimeError(f"ValStats: pred on {preds[b].device}, the accumulator on {dev}")
+            offs[b + 1] = offs[b] + preds[b].shape[0]
+        n = offs[bs]
+        self._result = None
+        tg = _as_f32_cuda(targets, dev) if targets.dim() == 2 and targets.shape[0] else None
+        nt, tcols = (tg.shape[0], tg.shape[1]) if tg is not None else (0, 0)
+        if nt:
+            self._tcls = self._grown(self._tcls, self.m, self.m + nt)
+            self._tcls[self.m:self.m + nt] = tg[:, 1]
+            self.m += nt
+        boxes = None
+        if want_boxes:
+            boxes = (torch.empty((n, 10), dtype=torch.float32, device=dev), torch.empty((n, 6), dtype=torch.float32, device=dev),
+                     torch.empty((n, 10), dtype=torch.float32, device=dev), torch.empty((n, 6), dtype=torch.float32, device=dev))
+        if n == 0:
+            return (boxes, offs) if want_boxes else None
+        packed = _pack_dets(preds, dev, n)
+        iv = _as_f32_cuda(iouv, dev)
+        self._rows = self._grown(self._rows, self.n, self.n + n)
+        cols = self.niou + 2
+        L = _lib.lib()
+        null = C.c_void_p(0)
+        with _lib.guard(dev):
+            st = _lib.stream_handle(dev)
+            ws = _lib.workspace(L.obb_val_tail_batch_workspace_bytes(n, nt), dev, st)
+            for b0 in range(0, bs, _TAIL_MAX_BS):
+                b1 = min(bs, b0 + _TAIL_MAX_BS)
+                k = b1 - b0
+                lo, hi = offs[b0], offs[b1]
+                if hi == lo:
+                    continue
+                doff = (C.c_int64 * (k + 1))(*[o - lo for o in offs[b0:b1 + 1]])
+                flat = []
+                for j in range(b0, b1):
+                    shape, ratio_pad = shapes[j][0], shapes[j][1]
+                    flat += (ratio_pad[1][0], ratio_pad[1][1], ratio_pad[0][0], shape[1], shape[0])
+                img5 = (C.c_float * (5 * k))(*flat)
+                tgk, ntk = tg, nt
+                if nt and (b0 or b1 < bs):                       # a chunk of a very large batch: its labels, re-based
+                    sel = (tg[:, 0] >= b0) & (tg[:, 0] < b1)
+                    tgk = tg[sel].clone()
+                    tgk[:, 0] -= b0
+                    ntk = int(tgk.shape[0])
+
+                def part(t, c, base=0):
+                    return C.c_void_p(t.data_ptr() + (base + lo) * c * 4)
+                rc = L.obb_val_tail_batch_f32(
+                    part(packed, 7), C.cast(doff, C.c_void_p), k, C.c_void_p(tgk.data_ptr()) if ntk else null, ntk, tcols,
+                    C.cast(img5, C.c_void_p), C.c_void_p(iv.data_ptr()), self.niou,
+                    part(boxes[0], 10) if boxes else null, part(boxes[1], 6) if boxes else null,
+                    part(boxes[2], 10) if boxes else null, part(boxes[3], 6) if boxes else null,
+                    part(self._rows, cols, self.n), C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(st))
+                _lib.check(rc, "obb_val_tail_batch_f32")
+        self.n += n
+        return (boxes, offs) if want_boxes else None
+
+    def _metrics(self):
+        if self._result is None:
+            from .utils import metrics
+            self._result = metrics.ap_from_rows(self.rows, self.target_cls, self.niou)
+        return self._result
+
+    def ap_per_class(self):
+        """utils.metrics.ap_per_class over everything added so far (the 7-tuple of numpy arrays)."""
+        return self._metrics()[0]
+
+    @property
+    def any_tp(self):
+        """val.py:270's guard `stats[0].any()`: a true positive at the first IoU level."""
+        return self._metrics()[1][1] > 0
+
+    def cpu(self):
+        """(correct bool (n, niou), conf (n), pcls (n), tcls (m)) numpy arrays: the four arrays of val.py:269."""
+        arr = self.rows.cpu().numpy()
+        return arr[:, :self.niou] > 0.5, arr[:, self.niou].copy(), arr[:, self.niou + 1].copy(), self.target_cls.cpu().numpy()

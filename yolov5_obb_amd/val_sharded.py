@@ -40,7 +40,7 @@ def _sync(device):
 
 
 def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True, single_cls=False, augment=False, device=None,
-        ap_per_class=None, names=None, nms=None, postprocess=None, match=None, niou=10, collect=True):
+        ap_per_class=None, names=None, nms=None, postprocess=None, match=None, niou=10, collect=True, device_metrics=False):
     """The loop of val.py:180-250 over ``loader`` (this rank's shard, see shard_loader), then the gather.
 
     model(im) -> (out (b, A, no), train_out), like the reference's Model in eval mode.  ``loader`` yields
@@ -50,7 +50,11 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
     Returns a dict: rank, world, seen (all ranks), dt (pre-process, inference, NMS seconds of the slowest rank), img_per_s
     (whole job), stats (rank 0: the four concatenated arrays in original image order), metrics (rank 0: what
     ap_per_class returned, or None).  collect=False: no exchange at all -- the rank's own seen / dt (a caller that only wants
-    the time buckets and does its own reduction, bench.py)."""
+    the time buckets and does its own reduction, bench.py).
+    device_metrics=True (CUDA, one process, the HIP tail): the statistics stay in device memory (val.ValStats) and the metrics
+    are this package's utils.metrics.ap_per_class over them -- ties among equal confidences by ascending row index, where the
+    reference's numpy leaves them unspecified; `ap_per_class` is not called, "stats" stays None, "val_stats" is the accumulator
+    and "metrics" its 7-tuple, or None when nothing matched (val.py:270)."""
     # the HIP path's tail runs once per BATCH (val.val_tail_batch: three launches, one copy); injected stand-ins keep the
     # reference's per-image loop
     batch_tail = None
@@ -69,6 +73,14 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
     device = torch.device(device)
     half = bool(half) and device.type != "cpu"                      # val.py:128
     iouv = torch.linspace(0.5, 0.95, niou, device=device)           # val.py:172
+    vstats = None
+    if device_metrics:
+        if world > 1:
+            # a stable tie order across ranks needs a global (image, row) key carried with every row
+            raise RuntimeError("val_sharded.run: device_metrics=True needs a single process (world size 1)")
+        if batch_tail is None or device.type != "cuda":
+            raise RuntimeError("val_sharded.run: device_metrics=True needs a CUDA device and this package's own tail")
+        vstats = V.ValStats(niou=niou, device=device)
     gidx = getattr(loader, "global_indices", None)
     per_image, dt, seen = [], [0.0, 0.0, 0.0], 0
     dt_batches = []                                                  # (pre-process, inference, NMS) seconds of every batch
@@ -93,6 +105,10 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
                 if single_cls:
                     for pred in out:
                         pred[:, 6] = 0
+                if vstats is not None:
+                    vstats.add_batch(out, targets, shapes, iouv)                 # rows and label classes stay on the device
+                    seen += len(out)
+                    continue
                 tail = batch_tail(out, targets, shapes, iouv)                    # val.py:209-250 for the whole batch
                 tc = targets[:, :2].cpu() if len(targets) else torch.zeros((0, 2))     # (image, class) of every label: one copy
                 for si, pred in enumerate(out):
@@ -136,6 +152,10 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
     if not collect:
         return {"rank": rank, "world": world, "seen": seen, "dt": list(dt), "img_per_s": seen / max(sum(dt), 1e-12), "stats": None,
                 "metrics": None, "dt_batches": dt_batches}
+    if vstats is not None:
+        metrics = vstats.ap_per_class()
+        return {"rank": rank, "world": world, "seen": seen, "dt": list(dt), "img_per_s": seen / max(sum(dt), 1e-12), "stats": None,
+                "metrics": metrics if vstats.any_tp else None, "dt_batches": dt_batches, "val_stats": vstats}
     # ---- the one exchange: per-image tuples to rank 0, in the original order of the image list
     if gidx is None:
         gidx = list(range(rank, rank + world * len(per_image), world)) if world > 1 else list(range(len(per_image)))
