@@ -146,3 +146,90 @@ def test_rbox2poly_and_hbb_match_reference(dev):
     p2 = rbox2poly(big.to(dev)).cpu()
     assert torch.allclose(p2, pyref.rbox2poly(big), rtol=1e-6, atol=2e-4)
     assert rbox2poly(torch.zeros(0, 5, device=dev)).shape == (0, 8)
+
+
+def _csl_labels(n):
+    """Every integer label from -(n + 2) to n + 2, the float32 neighbours of each and the half-way points: int(n/2 - label)
+    steps at every one of them, and |n/2 - label| crosses n (the window is then left unrolled) at -n/2 and 3n/2."""
+    i = np.arange(-(n + 2), n + 3, dtype=np.float32)
+    lab = np.concatenate([i, np.nextafter(i, np.float32(-np.inf)), np.nextafter(i, np.float32(np.inf)), i + np.float32(0.5),
+                          np.float32([n, -n, n + 0.5, -(n + 0.5), 1.5 * n, -0.5 * n, 1.5 * n + 1, -0.5 * n - 1])])
+    return lab.astype(np.float32)
+
+
+@pytest.mark.parametrize("sig", [0.5, 6.0])
+@pytest.mark.parametrize("u", [0.0, 0.5, -3.0])
+@pytest.mark.parametrize("num_class", [1, 2, 90, 181])
+def test_csl_encode_window_sizes_offsets_and_widths(dev, num_class, u, sig):
+    """obb_csl_encode_f32 away from num_class = 180, u = 0: odd window sizes (n / 2 is no integer), a window of one bin, a shifted
+    and a narrow Gaussian, labels on and next to every integer and beyond +-num_class."""
+    from yolov5_obb_amd.utils.rboxs_utils import csl_encode
+    lab = _csl_labels(num_class)
+    got = csl_encode(torch.from_numpy(lab).to(dev), num_class, u, sig).cpu().numpy()
+    ref = np.stack([pyref.gaussian_label(float(a), num_class, u, sig) for a in lab]).astype(np.float32)
+    assert got.shape == ref.shape == (len(lab), num_class)
+    assert np.allclose(got, ref, rtol=1e-6, atol=1e-30), np.abs(got - ref).max()
+    assert np.array_equal(got.argmax(1), ref.argmax(1))
+
+
+def _poly_f64(rb):
+    """utils/rboxs_utils.py:106-145 and :147-181 in float64 on the float32 inputs."""
+    x, y, w, h, th = (rb[:, k].astype(np.float64) for k in range(5))
+    c, s = np.cos(th), np.sin(th)
+    v1x, v1y, v2x, v2y = w / 2 * c, -w / 2 * s, -h / 2 * s, -h / 2 * c
+    poly = np.stack([x + v1x + v2x, y + v1y + v2y, x + v1x - v2x, y + v1y - v2y, x - v1x - v2x, y - v1y - v2y, x - v1x + v2x, y - v1y + v2y], 1)
+    px, py = poly[:, 0::2], poly[:, 1::2]
+    hbb = np.stack([(px.max(1) + px.min(1)) / 2, (py.max(1) + py.min(1)) / 2, px.max(1) - px.min(1), py.max(1) - py.min(1)], 1)
+    return poly, hbb
+
+
+@pytest.mark.parametrize("want", ["poly", "hbb"])
+@pytest.mark.parametrize("n", [1, 257, 3001])
+def test_rbox2poly_row_stride_and_single_outputs(dev, n, want):
+    """obb_rbox2poly_f32 through the C ABI on (n, 7) rows (row_stride = 7: the NMS output [x y l s theta conf cls]) with only one
+    of the two outputs requested; |theta| up to 4 pi, sides from 1e-3 to 4096.  The output sits between guard bytes.
+
+    Each formula is compared with its float64 evaluation under the file's tolerance: the polygon (utils/rboxs_utils.py:106-145)
+    on the boxes, the hull (:147-181) on the float32 polygon it is computed from, as the reference computes it.  The hull of the
+    float64 polygon is no reference for that tolerance: a hull extent is the difference of two float32 corners of magnitude up
+    to 3000 (half an ulp each: 1.2e-4), measured 1.20 x (1e-4 + 1e-6 |ref|) on a 4096 x 1e-3 box; it is held to twice the
+    polygon's tolerance instead."""
+    import ctypes as C
+    from yolov5_obb_amd import _lib
+    rng = np.random.default_rng(100 + n)
+    rb = np.zeros((n, 7), np.float32)
+    rb[:, 0:2] = rng.uniform(0.0, 1024.0, (n, 2))
+    rb[:, 2:4] = np.exp(rng.uniform(np.log(1e-3), np.log(4096.0), (n, 2)))
+    rb[:, 4] = rng.uniform(-4 * np.pi, 4 * np.pi, n)
+    rb[:, 5:7] = rng.uniform(1e6, 2e6, (n, 2))                       # a kernel reading columns 5, 6 as the next row's x, y shows
+    rb[0, 2:5] = (4096.0, 1e-3, 4 * np.pi)
+    poly_ref, hbb_ref = _poly_f64(rb)
+    width, guard, fill = (8, 64, 0x5A) if want == "poly" else (4, 64, 0x5A)
+    raw = torch.full(((2 * guard + n * width) * 4,), fill, dtype=torch.uint8, device=dev)
+    out = raw[guard * 4:(guard + n * width) * 4].view(torch.float32)
+    d = torch.from_numpy(rb).to(dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().obb_rbox2poly_f32(_lib.ptr(d), n, 7, _lib.ptr(out) if want == "poly" else None, _lib.ptr(out) if want == "hbb" else None,
+                                          _lib.stream_ptr(dev))
+    assert rc == 0
+    torch.cuda.synchronize(dev)
+    assert bool((raw[:guard * 4] == fill).all()) and bool((raw[(guard + n * width) * 4:] == fill).all())
+    got = out.view(n, width).cpu().numpy().astype(np.float64)
+    if want == "poly":
+        ref = poly_ref
+    else:
+        poly = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            assert _lib.lib().obb_rbox2poly_f32(_lib.ptr(d), n, 7, _lib.ptr(poly), None, _lib.stream_ptr(dev)) == 0
+        p = poly.cpu().numpy().astype(np.float64)
+        assert np.allclose(p, poly_ref, rtol=1e-6, atol=1e-4)
+        px, py = p[:, 0::2], p[:, 1::2]
+        ref = np.stack([(px.max(1) + px.min(1)) / 2, (py.max(1) + py.min(1)) / 2, px.max(1) - px.min(1), py.max(1) - py.min(1)], 1)
+        bound = 2.0 * (1e-4 + 1e-6 * np.abs(poly_ref).max(1, keepdims=True))
+        assert (np.abs(got - hbb_ref) <= bound).all(), (np.abs(got - hbb_ref) / bound).max()
+    err = np.abs(got - ref) / (1e-4 + 1e-6 * np.abs(ref))
+    print(f"rbox2poly {want} n={n}: max |got - ref| / (1e-4 + 1e-6 |ref|) = {err.max():.3f}")
+    assert np.allclose(got, ref, rtol=1e-6, atol=1e-4), err.max()
+    with torch.cuda.device(dev):                                     # neither output: an error, nothing is launched
+        assert _lib.lib().obb_rbox2poly_f32(_lib.ptr(d), n, 7, None, None, _lib.stream_ptr(dev)) == -1
+        assert _lib.lib().obb_rbox2poly_f32(_lib.ptr(d), n, 4, _lib.ptr(out), None, _lib.stream_ptr(dev)) == -1
