@@ -466,6 +466,32 @@ size_t obb_process_batch_workspace_bytes(int64_t n, int64_t m);
 int obb_process_batch_f32(const float* det6, int64_t n, const float* lab5, int64_t m, const float* iouv, int niou, uint8_t* correct,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ConfusionMatrix.process_batch (utils/metrics.py:117-163) on the device, one launch per batch, one workgroup per image.
+ * Per image: detections with conf > conf_thres (strict; NaN fails) against the labels; a pair is a candidate iff box_iou >
+ * iou_thres (strict, float32; both thresholds are taken as float32, as torch compares a float32 tensor with a Python scalar).
+ * TIE RULE (the reference's numpy argsort leaves equal IoUs in an unspecified order; pinned here to the reference's own lines with
+ * every argsort stable): each kept detection chooses its candidate label of highest IoU, ties to the HIGHER label index; each
+ * label keeps, among the detections that chose it, the one of highest IoU, ties to the HIGHER detection index (indices = positions
+ * in the image's own lists).  Then, as the reference: a label with a winner d adds 1 to matrix[cls_d][cls_l] whether or not the
+ * classes agree, a label without one to matrix[nc][cls_l]; a kept detection that won no label adds 1 to matrix[cls_d][nc], but
+ * only in an image with at least one match.  Only images with at least one detection row AND one label take part (val.py:217-246).
+ *   matrix_i64  (nc + 1)^2 + 1 device int64, row-major [predicted][true]; ACCUMULATED into, never zeroed by the call.  The last
+ *               element counts the cells that could not be taken because a class, truncated like .int(), lies outside [0, nc)
+ *               (the reference raises IndexError or wraps a negative index); such a row still takes part in the matching.
+ *   1 <= nc <= 32767.  An LDS histogram per workgroup when (nc + 1)^2 <= 12100 (nc <= 109), global atomics per count above.
+ *   Per-image counts up to 32767 are the contract (the reference's astype(np.int16) wrap above that is not reproduced).
+ * obb_confusion_batch_f32 takes the inputs of obb_val_tail_batch_f32 (bs <= 64, packed det7, targets, img5_host) and computes
+ * the same boxes (pred_hbbn, the label boxes), so both run back to back on the same arrays.  obb_confusion_process_batch_f32 is
+ * the reference's per-image signature on boxes already computed: det6 (n,6) [x1 y1 x2 y2 conf cls], lab5 (m,5) [cls x1 y1 x2 y2].
+ * Stream-ordered, no synchronisation; the argument checks answer before any device call; no detections or no labels: OBB_OK,
+ * no launch.  The workspace (obb_confusion_workspace_bytes of the call's n and nt / m) is linear in both. */
+size_t obb_confusion_workspace_bytes(int64_t n_det, int64_t nt);
+int obb_confusion_batch_f32(const float* det7, const int64_t* det_off_host, int64_t bs, const float* targets, int64_t nt, int64_t tcols,
+                            const float* img5_host, int nc, float conf_thres, float iou_thres, int64_t* matrix_i64, void* ws,
+                            size_t ws_bytes, void* stream);
+int obb_confusion_process_batch_f32(const float* det6, int64_t n, const float* lab5, int64_t m, int nc, float conf_thres, float iou_thres,
+                                    int64_t* matrix_i64, void* ws, size_t ws_bytes, void* stream);
+
 /* ap_per_class (utils/metrics.py:21-114, compute_ap method 'interp') over statistics that stay on the device.  stats = n rows
  * [correct x niou as 0 / 1, conf, cls] with row_stride >= niou + 2 floats -- the rows obb_val_tail_batch_f32 writes; target_cls =
  * the class of every label (m floats).  Class ids are integers 0 .. nc_max - 1, nc_max <= 256; 1 <= niou <= 16; n, m < 2^31 - 1.

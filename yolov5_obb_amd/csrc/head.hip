@@ -16,6 +16,7 @@
 #include "obb_hip.h"
 #include "dtype_device.h"
 #include "detect_math.h"
+#include "confusion_math.h"
 
 namespace obb {
 
@@ -598,6 +599,176 @@ __global__ void k_vt_stats(const float* __restrict__ det7, const int* __restrict
   }
 }
 
+// ---- ConfusionMatrix.process_batch (utils/metrics.py:125-163) for every image of a batch in ONE launch: a workgroup is an
+// image, workgroups exchange nothing, and the only traffic between them is the final atomic adds into the matrix.  The rules
+// (strict compares, the pinned tie order) are csrc/confusion_math.h; the boxes are the bytes of pred_hbbn (vt_post_one) and of
+// k_vt_dets' label boxes (vt_label_box).  kBatch = false: one image on boxes already computed (det6 / lab5), the same core.
+//   phase 0  the image's labels, in the order of `targets`, boxes computed once -> workspace; its detections -> workspace
+//   phase 1  label tiles of kVtLabLds boxes through LDS; every kept detection keeps its best candidate label (rule 1)
+//   phase 2  one 64-bit atomic max per matched detection into its label's winner slot (rule 2); block-wide "any match"
+//   phase 3  labels: the winner's cell, else the background row          phase 4  detections that won nothing: background column
+// Winner slots: LDS when the image has <= kVtLabLds labels, else the workspace.  Cells: an LDS histogram, flushed with one global
+// atomic per non-zero cell, when (nc + 1)^2 <= kCmHistLds (nc <= 109); else global atomics directly.  Per-image counts < 2^32.
+constexpr int kCmThreads = 1024;
+constexpr int kCmHistLds = 110 * 110;      // 48,400 B beside the 14 KiB of label tile and slots: 61.4 KiB, two workgroups in a CU's 160 KiB
+struct CmWs {                              // the call's workspace, carved by cm_carve (labels by position, detections by packed row)
+  unsigned long long* win;                 // [nt] winner slot per label
+  float* lbox; int* lcls;                  // [nt][4], [nt] class index or -1
+  float* dbox; int* dcls;                  // [n][4], [n] class index or -1
+  float* biou; int* blab;                  // [n] best candidate label (position in the image's list), -1 none, -2 dropped by conf
+};
+template <bool kBatch>
+__global__ __launch_bounds__(kCmThreads) void k_confusion(const float* __restrict__ dets, ValTailImgs im, int n1,
+                                                          const float* __restrict__ labels, int nt, int tcols, int nc, float conf_thres,
+                                                          float iou_thres, unsigned long long* __restrict__ matrix, CmWs ws) {
+  __shared__ float s_lab[kVtLabLds][4];
+  __shared__ int s_lc[kVtLabLds];
+  __shared__ unsigned long long s_win[kVtLabLds];
+  __shared__ unsigned int s_hist[kCmHistLds];
+  __shared__ int s_wave[kCmThreads / 64][2];
+  __shared__ int s_any, s_oor;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int kWaves = kCmThreads / 64;
+  const int b = blockIdx.x;
+  const int d0 = kBatch ? im.det_off[b] : 0;                     // first packed row of the image's detections
+  const int n = kBatch ? im.det_off[b + 1] - d0 : n1;
+  if (n == 0) return;                                            // val.py:217-220: no detections, nothing is counted
+  // ---- the image's labels: m of them, stored from position l0 of the label arrays (= the labels of earlier images: disjoint ranges)
+  int m = nt, l0 = 0;
+  if (kBatch) {
+    int eq = 0, less = 0;
+    for (int l = tid; l < nt; l += kCmThreads) {
+      const int lb = (int)labels[(size_t)l * tcols];
+      eq += lb == b; less += lb >= 0 && lb < b;
+    }
+    for (int o = 32; o; o >>= 1) { eq += __shfl_xor(eq, o); less += __shfl_xor(less, o); }
+    if (lane == 0) { s_wave[wave][0] = eq; s_wave[wave][1] = less; }
+    __syncthreads();
+    m = 0;
+    for (int w = 0; w < kWaves; w++) { m += s_wave[w][0]; l0 += s_wave[w][1]; }
+    __syncthreads();
+  }
+  if (m == 0) return;                                            // val.py:238: no labels, nothing is counted
+  const bool win_lds = m <= kVtLabLds, hist_lds = (nc + 1) * (nc + 1) <= kCmHistLds;
+  const int cells = (nc + 1) * (nc + 1);
+  if (tid == 0) { s_any = 0; s_oor = 0; }
+  if (win_lds) for (int l = tid; l < m; l += kCmThreads) s_win[l] = 0ull;
+  if (hist_lds) for (int c = tid; c < cells; c += kCmThreads) s_hist[c] = 0u;
+  // phase 0, labels: ordered compaction of the rows with t[0] == b, kCmThreads rows a trip (the tie rule needs their order)
+  for (int base = 0, at = 0; base < nt; base += kCmThreads) {
+    const int l = base + tid;
+    const float* t = labels + (size_t)l * (kBatch ? tcols : 5);
+    const bool mine = l < nt && (!kBatch || (int)t[0] == b);
+    const unsigned long long bal = __ballot(mine);
+    if (kBatch) {
+      if (lane == 0) s_wave[wave][0] = __popcll(bal);
+      __syncthreads();
+    }
+    int pos = at + __popcll(bal & ((1ull << lane) - 1ull)), total = 0;
+    if (kBatch) {
+      for (int w = 0; w < kWaves; w++) { const int c = s_wave[w][0]; if (w < wave) pos += c; total += c; }
+    } else {
+      pos = l;
+    }
+    if (mine) {
+      float* o = ws.lbox + (size_t)(l0 + pos) * 4;
+      if (kBatch) {
+        float bx[4];
+        vt_label_box(t, im, b, bx);
+        o[0] = bx[0]; o[1] = bx[1]; o[2] = bx[2]; o[3] = bx[3];
+      } else {
+        o[0] = t[1]; o[1] = t[2]; o[2] = t[3]; o[3] = t[4];
+      }
+      ws.lcls[l0 + pos] = cm::class_index(t[kBatch ? 1 : 0], nc);
+      if (!win_lds) __hip_atomic_store(&ws.win[l0 + pos], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    at += total;
+    if (kBatch) __syncthreads();                                 // (s_wave is rewritten by the next trip)
+  }
+  // phase 0, detections: pred_hbbn's box, the class index and the conf filter
+  for (int d = tid; d < n; d += kCmThreads) {
+    float bx[4], conf, cls;
+    if (kBatch) {
+      const float* row = dets + ((size_t)im.det_row[b] + d) * 7;
+      vt_post_one(row, 0, im.pad_x[b], im.pad_y[b], im.gain[b], nullptr, nullptr, nullptr, nullptr, bx);
+      conf = row[5]; cls = row[6];
+    } else {
+      const float* row = dets + (size_t)d * 6;
+      bx[0] = row[0]; bx[1] = row[1]; bx[2] = row[2]; bx[3] = row[3]; conf = row[4]; cls = row[5];
+    }
+    float* o = ws.dbox + (size_t)(d0 + d) * 4;
+    o[0] = bx[0]; o[1] = bx[1]; o[2] = bx[2]; o[3] = bx[3];
+    ws.dcls[d0 + d] = cm::class_index(cls, nc);
+    ws.biou[d0 + d] = 0.f;
+    ws.blab[d0 + d] = cm::keeps(conf, conf_thres) ? -1 : -2;
+  }
+  __syncthreads();
+  // phase 1: a tile of labels in LDS, every thread's detections against it (a thread meets only its own detections' records)
+  for (int t0 = 0; t0 < m; t0 += kVtLabLds) {
+    const int tn = m - t0 < kVtLabLds ? m - t0 : kVtLabLds;
+    for (int k = tid; k < tn; k += kCmThreads) {
+      const float* q = ws.lbox + (size_t)(l0 + t0 + k) * 4;
+      s_lab[k][0] = q[0]; s_lab[k][1] = q[1]; s_lab[k][2] = q[2]; s_lab[k][3] = q[3];
+      s_lc[k] = ws.lcls[l0 + t0 + k];
+    }
+    __syncthreads();
+    for (int d = tid; d < n; d += kCmThreads) {
+      int bl = ws.blab[d0 + d];
+      if (bl == -2) continue;
+      float bi = ws.biou[d0 + d];
+      const float* q = ws.dbox + (size_t)(d0 + d) * 4;
+      const float b2[4] = {q[0], q[1], q[2], q[3]};
+      for (int k = 0; k < tn; k++) {
+        float iou;
+        if (cm::candidate(s_lab[k], b2, iou_thres, &iou) && cm::better_label(iou, t0 + k, bi, bl)) { bi = iou; bl = t0 + k; }
+      }
+      ws.biou[d0 + d] = bi; ws.blab[d0 + d] = bl;
+    }
+    __syncthreads();
+  }
+  // phase 2: the winner of every label
+  for (int d = tid; d < n; d += kCmThreads) {
+    const int bl = ws.blab[d0 + d];
+    if (bl < 0) continue;
+    const unsigned long long key = cm::winner_key(ws.biou[d0 + d], d);
+    if (win_lds) atomicMax(&s_win[bl], key); else atomicMax(&ws.win[l0 + bl], key);
+    s_any = 1;
+  }
+  __syncthreads();
+  const bool any = s_any != 0;
+  auto winner_of = [&](int l) {
+    return win_lds ? s_win[l] : __hip_atomic_load(&ws.win[l0 + l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  auto count = [&](int row, int col) {                           // matrix[predicted][true] += 1; a class outside [0, nc): the counter
+    if (row < 0 || col < 0) { atomicAdd(&s_oor, 1); return; }
+    const int c = row * (nc + 1) + col;
+    if (hist_lds) atomicAdd(&s_hist[c], 1u); else atomicAdd(&matrix[c], 1ull);
+  };
+  // phase 3: labels
+  for (int l = tid; l < m; l += kCmThreads) {
+    const unsigned long long key = winner_of(l);
+    const int lc = ws.lcls[l0 + l];
+    if (key) count(ws.dcls[d0 + cm::winner_det(key)], lc);       // taken whether or not the classes agree (metrics.py:156)
+    else count(nc, lc);                                          // background row (metrics.py:158)
+  }
+  // phase 4: kept detections that are no label's winner -- only in an image with a match (`if n:`, metrics.py:160)
+  if (any) {
+    for (int d = tid; d < n; d += kCmThreads) {
+      const int bl = ws.blab[d0 + d];
+      if (bl == -2) continue;
+      if (bl < 0 || cm::winner_det(winner_of(bl)) != d) count(ws.dcls[d0 + d], nc);
+    }
+  }
+  __syncthreads();
+  if (hist_lds) {
+    for (int c = tid; c < cells; c += kCmThreads) {
+      const unsigned int v = s_hist[c];
+      if (v) atomicAdd(&matrix[c], (unsigned long long)v);
+    }
+  }
+  if (tid == 0 && s_oor) atomicAdd(&matrix[cells], (unsigned long long)s_oor);
+}
+
 }  // namespace obb
 
 extern "C" {
@@ -615,14 +786,10 @@ size_t obb_val_tail_batch_workspace_bytes(int64_t n_det, int64_t nt) {
   return (size_t)(n_det > 0 ? n_det : 1) * 8 + (size_t)(nt > 0 ? nt : 1) * 20 + 512;
 }
 
-static int val_tail_batch_impl(const float* det7, const int64_t* det_row_host, const int64_t* det_off_host, int64_t bs, const float* targets, int64_t nt, int64_t tcols,
-                               const float* img5_host, const float* iouv, int niou, float* poly10, float* hbb6, float* polyn10,
-                               float* hbbn6, float* stats, void* ws, size_t ws_bytes, void* stream, int64_t* done) {
-  if (bs < 1 || bs > obb::kValTailMaxBs || nt < 0 || niou < 1 || !det_off_host || !img5_host || !iouv) return OBB_ERR_BAD_ARG;
-  if (nt > 0 && (!targets || tcols < 7)) return OBB_ERR_BAD_ARG;
+// the per-image table of a batch call from its host arrays (det_row_host NULL: packed detections); OBB_ERR_BAD_ARG when they are inconsistent
+static int vt_fill_imgs(obb::ValTailImgs& im, const int64_t* det_row_host, const int64_t* det_off_host, int64_t bs, const float* img5_host) {
   const int64_t n = det_off_host[bs];
-  if (n < 0 || n > 0x7fffffff || nt > 0x7fffffff || det_off_host[0] != 0) return OBB_ERR_BAD_ARG;
-  obb::ValTailImgs im;
+  if (n < 0 || n > 0x7fffffff || det_off_host[0] != 0) return OBB_ERR_BAD_ARG;
   im.bs = (int)bs;
   for (int b = 0; b <= (int)bs; b++) {
     if (b > 0 && det_off_host[b] < det_off_host[b - 1]) return OBB_ERR_BAD_ARG;
@@ -638,6 +805,18 @@ static int val_tail_batch_impl(const float* det7, const int64_t* det_row_host, c
     if (!(q[2] > 0.f)) return OBB_ERR_BAD_ARG;
     im.pad_x[b] = q[0]; im.pad_y[b] = q[1]; im.gain[b] = q[2]; im.shape_w[b] = q[3]; im.shape_h[b] = q[4];
   }
+  return OBB_OK;
+}
+
+static int val_tail_batch_impl(const float* det7, const int64_t* det_row_host, const int64_t* det_off_host, int64_t bs, const float* targets, int64_t nt, int64_t tcols,
+                               const float* img5_host, const float* iouv, int niou, float* poly10, float* hbb6, float* polyn10,
+                               float* hbbn6, float* stats, void* ws, size_t ws_bytes, void* stream, int64_t* done) {
+  if (bs < 1 || bs > obb::kValTailMaxBs || nt < 0 || niou < 1 || !det_off_host || !img5_host || !iouv) return OBB_ERR_BAD_ARG;
+  if (nt > 0 && (!targets || tcols < 7)) return OBB_ERR_BAD_ARG;
+  if (nt > 0x7fffffff) return OBB_ERR_BAD_ARG;
+  obb::ValTailImgs im;
+  if (vt_fill_imgs(im, det_row_host, det_off_host, bs, img5_host) != OBB_OK) return OBB_ERR_BAD_ARG;
+  const int64_t n = det_off_host[bs];
   if (n == 0) { if (done) *done = 0; return OBB_OK; }            // (host-visible memory: nothing to wait for)
   if (!det7 || !stats) return OBB_ERR_BAD_ARG;
   if (!ws || ws_bytes < obb_val_tail_batch_workspace_bytes(n, nt)) return OBB_ERR_WORKSPACE;
@@ -690,6 +869,53 @@ int obb_process_batch_f32(const float* det6, int64_t n, const float* lab5, int64
   if (hipMemsetAsync(winner, 0x7f, (size_t)(m > 0 ? m : 1) * 4, st) != hipSuccess) return OBB_ERR_LAUNCH;
   obb::k_pb_best<<<(unsigned)((n + 127) / 128), 128, 0, st>>>(det6, (int)n, lab5, (int)m, iouv, best_label, best_iou, winner);
   obb::k_pb_correct<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(best_label, best_iou, winner, iouv, (int)n, niou, correct);
+  return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
+}
+
+size_t obb_confusion_workspace_bytes(int64_t n_det, int64_t nt) {
+  return (size_t)(n_det > 0 ? n_det : 1) * 28 + (size_t)(nt > 0 ? nt : 1) * 28 + 256;
+}
+
+// the arrays of obb::CmWs in a workspace of obb_confusion_workspace_bytes(n, nt) bytes (the 8-byte slots first, on an 8-byte boundary)
+static obb::CmWs cm_carve(void* ws, int64_t n, int64_t nt) {
+  const size_t nn = (size_t)(n > 0 ? n : 1), ll = (size_t)(nt > 0 ? nt : 1);
+  obb::CmWs w;
+  w.win = (unsigned long long*)(((uintptr_t)ws + 7) & ~(uintptr_t)7);
+  w.lbox = (float*)(w.win + ll);
+  w.lcls = (int*)(w.lbox + 4 * ll);
+  w.dbox = (float*)(w.lcls + ll);
+  w.dcls = (int*)(w.dbox + 4 * nn);
+  w.biou = (float*)(w.dcls + nn);
+  w.blab = (int*)(w.biou + nn);
+  return w;
+}
+
+int obb_confusion_batch_f32(const float* det7, const int64_t* det_off_host, int64_t bs, const float* targets, int64_t nt, int64_t tcols,
+                            const float* img5_host, int nc, float conf_thres, float iou_thres, int64_t* matrix_i64, void* ws,
+                            size_t ws_bytes, void* stream) {
+  if (bs < 1 || bs > obb::kValTailMaxBs || nt < 0 || nt > 0x7fffffff || nc < 1 || nc > 32767 || !det_off_host || !img5_host || !matrix_i64)
+    return OBB_ERR_BAD_ARG;
+  if (nt > 0 && (!targets || tcols < 7)) return OBB_ERR_BAD_ARG;
+  obb::ValTailImgs im;
+  if (vt_fill_imgs(im, nullptr, det_off_host, bs, img5_host) != OBB_OK) return OBB_ERR_BAD_ARG;
+  const int64_t n = det_off_host[bs];
+  if (n == 0 || nt == 0) return OBB_OK;                          // no image has both detections and labels: nothing is counted
+  if (!det7) return OBB_ERR_BAD_ARG;
+  if (!ws || ws_bytes < obb_confusion_workspace_bytes(n, nt)) return OBB_ERR_WORKSPACE;
+  obb::k_confusion<true><<<(unsigned)bs, obb::kCmThreads, 0, (hipStream_t)stream>>>(
+      det7, im, 0, targets, (int)nt, (int)tcols, nc, conf_thres, iou_thres, reinterpret_cast<unsigned long long*>(matrix_i64), cm_carve(ws, n, nt));
+  return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
+}
+
+int obb_confusion_process_batch_f32(const float* det6, int64_t n, const float* lab5, int64_t m, int nc, float conf_thres, float iou_thres,
+                                    int64_t* matrix_i64, void* ws, size_t ws_bytes, void* stream) {
+  if (n < 0 || m < 0 || n > 0x7fffffff || m > 0x7fffffff || nc < 1 || nc > 32767 || !matrix_i64) return OBB_ERR_BAD_ARG;
+  if (n == 0 || m == 0) return OBB_OK;
+  if (!det6 || !lab5) return OBB_ERR_BAD_ARG;
+  if (!ws || ws_bytes < obb_confusion_workspace_bytes(n, m)) return OBB_ERR_WORKSPACE;
+  obb::ValTailImgs im = {};                                      // (not read by the one-image form)
+  obb::k_confusion<false><<<1, obb::kCmThreads, 0, (hipStream_t)stream>>>(
+      det6, im, (int)n, lab5, (int)m, 5, nc, conf_thres, iou_thres, reinterpret_cast<unsigned long long*>(matrix_i64), cm_carve(ws, n, m));
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 

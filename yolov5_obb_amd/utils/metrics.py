@@ -6,7 +6,12 @@ introsort, so tied rows land in an unspecified order and its AP moves with it (b
 confidences).  Here ties are broken by ASCENDING ROW INDEX -- ``np.argsort(-conf, kind='stable')`` -- like every score sort
 of this package.  Everything else is numpy's arithmetic in double, operation for operation.
 
-Opt-in: ``dropin.install()`` does not replace the reference's function."""
+``ConfusionMatrix`` (:117-163 of the reference) is the other class of that file that lives here: one launch of
+``obb_confusion_batch_f32`` per batch (csrc/head.hip: k_confusion) into counters that stay on the device.  Its deliberate
+difference is of the same kind: the reference orders equal IoUs with ``matches[:, 2].argsort()[::-1]``, numpy's unstable
+sort; here every argsort is stable (the rule is written out on the class).
+
+Opt-in: ``dropin.install()`` does not replace the reference's function or class."""
 import numpy as np
 import torch
 
@@ -89,3 +94,147 @@ def ap_per_class(tp, conf, pred_cls, target_cls, plot=False, save_dir='.', names
         raise RuntimeError("ap_per_class: tp, conf and pred_cls must have the same number of rows")
     rows = torch.cat((tp, conf[:, None], pred_cls[:, None]), 1)
     return ap_from_rows(rows, _to_dev(target_cls, dev).reshape(-1), niou)[0]
+
+
+class ConfusionMatrix:
+    """The reference's ConfusionMatrix (utils/metrics.py:117-163) with the counters in device memory: process_batch / add_batch
+    launch one kernel and return; nothing is copied and nothing waits until `.matrix` is read.
+
+    Per image: detections with conf > self.conf against the labels, a pair is a candidate iff box_iou > self.iou_thres (both
+    strict, in float32).  TIES, where the reference's numpy sort leaves the order unspecified, are pinned to the reference's own
+    lines with every argsort stable: a detection chooses its candidate label of highest IoU, ties to the HIGHER label index;
+    a label keeps, among the detections that chose it, the one of highest IoU, ties to the HIGHER detection index.  The fill is
+    the reference's, quirks included: the winner's cell is taken whether or not the classes agree, an unmatched label counts in
+    the background row, an unmatched kept detection in the background column -- but only in an image with at least one match.
+    A class outside [0, nc) touches no cell and makes the next read of `.matrix` raise (the reference raises IndexError, or
+    wraps a negative index silently).  Per-image counts up to 32767 (the reference's int16 wrap above is not reproduced)."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45, device=None):
+        self.nc = int(nc)  # number of classes
+        self.conf = conf
+        self.iou_thres = iou_thres
+        if self.nc < 1:
+            raise RuntimeError(f"ConfusionMatrix: nc must be >= 1, got {nc}")
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != "cuda":
+            raise RuntimeError("ConfusionMatrix: device must be a CUDA/HIP device (no CPU path, by design)")
+        self._mat = None                   # (nc + 1)^2 + 1 int64 on the device, made at the first batch; the last one counts bad classes
+
+    def _counters(self, dev):
+        if self._mat is None:
+            if self.device is None:
+                self.device = dev
+            self._mat = torch.zeros((self.nc + 1) ** 2 + 1, dtype=torch.int64, device=self.device)
+        if dev != self._mat.device:
+            raise RuntimeError(f"ConfusionMatrix: input on {dev}, the counters on {self._mat.device}")
+        return self._mat
+
+    def process_batch(self, detections, labels):
+        """
+        Arguments:
+            detections (Array[N, 6]), x1, y1, x2, y2, conf, class   (CUDA)
+            labels (Array[M, 5]), class, x1, y1, x2, y2             (moved to the detections' device when they are elsewhere)
+        Returns:
+            None, updates confusion matrix accordingly (asynchronously)
+        """
+        _lib.require_cuda(detections, "detections")
+        dev = detections.device
+        if detections.dim() != 2 or detections.shape[1] != 6 or labels.dim() != 2 or labels.shape[1] != 5:
+            raise RuntimeError(f"ConfusionMatrix: detections (n, 6) and labels (m, 5), got {tuple(detections.shape)} and {tuple(labels.shape)}")
+        mat = self._counters(dev)
+        n, m = int(detections.shape[0]), int(labels.shape[0])
+        if n == 0 or m == 0:
+            return
+        det = detections.to(torch.float32).contiguous()
+        lab = labels.to(device=dev, dtype=torch.float32).contiguous()
+        L = _lib.lib()
+        with _lib.guard(dev):
+            st = _lib.stream_handle(dev)
+            ws = _lib.workspace(L.obb_confusion_workspace_bytes(n, m), dev, st)
+            rc = L.obb_confusion_process_batch_f32(_lib.ptr(det), n, _lib.ptr(lab), m, self.nc, float(self.conf), float(self.iou_thres),
+                                                   _lib.ptr(mat), _lib.ptr(ws), ws.numel(), st)
+        _lib.check(rc, "obb_confusion_process_batch_f32")
+
+    def _launch(self, L, det_ptr, doff, k, n, tg_ptr, nt, tcols, img5, dev, st):
+        """One obb_confusion_batch_f32 on arrays the caller has laid out for obb_val_tail_batch_f32 (<= 64 images)."""
+        mat = self._counters(dev)
+        if n == 0 or nt == 0:
+            return
+        ws = _lib.workspace(L.obb_confusion_workspace_bytes(n, nt), dev, st)
+        rc = L.obb_confusion_batch_f32(det_ptr, doff, k, tg_ptr, nt, tcols, img5, self.nc, float(self.conf), float(self.iou_thres),
+                                       _lib.ptr(mat), _lib.ptr(ws), ws.numel(), st)
+        _lib.check(rc, "obb_confusion_batch_f32")
+
+    def add_batch(self, preds, targets, shapes):
+        """process_batch for ALL images of a batch in one launch, from the arguments of val.val_tail_batch: preds list of (n_i, 7)
+        CUDA tensors [x y l s theta conf cls] (consecutive views of non_max_suppression_obb's packed buffer are used in place),
+        targets (nt, >= 7) [img cls cx cy l s theta ...], shapes per image ((h, w), ((gain, gain), (pad_x, pad_y))).  The boxes
+        are those of val.py:226-243 (pred_hbbn, labels_hbbn); images without detections or without labels add nothing."""
+        import ctypes as C
+        from ..val import _TAIL_MAX_BS, _as_f32_cuda, _pack_dets
+        bs = len(preds)
+        if bs == 0:
+            return
+        _lib.require_cuda(preds[0], "pred")
+        dev = preds[0].device
+        offs = [0] * (bs + 1)
+        for b in range(bs):
+            offs[b + 1] = offs[b] + preds[b].shape[0]
+        n = offs[bs]
+        self._counters(dev)
+        tg = _as_f32_cuda(targets, dev) if targets.dim() == 2 and targets.shape[0] else None
+        if n == 0 or tg is None:
+            return
+        nt, tcols = tg.shape
+        packed = _pack_dets(preds, dev, n)
+        L = _lib.lib()
+        with _lib.guard(dev):
+            st = _lib.stream_handle(dev)
+            for b0 in range(0, bs, _TAIL_MAX_BS):
+                b1 = min(bs, b0 + _TAIL_MAX_BS)
+                k = b1 - b0
+                lo, hi = offs[b0], offs[b1]
+                if hi == lo:
+                    continue
+                doff = (C.c_int64 * (k + 1))(*[o - lo for o in offs[b0:b1 + 1]])
+                flat = []
+                for j in range(b0, b1):
+                    shape, ratio_pad = shapes[j][0], shapes[j][1]
+                    flat += (ratio_pad[1][0], ratio_pad[1][1], ratio_pad[0][0], shape[1], shape[0])
+                img5 = (C.c_float * (5 * k))(*flat)
+                tgk, ntk = tg, nt
+                if b0 or b1 < bs:                                # a chunk of a very large batch: its labels, re-based
+                    sel = (tg[:, 0] >= b0) & (tg[:, 0] < b1)
+                    tgk = tg[sel].clone()
+                    tgk[:, 0] -= b0
+                    ntk = int(tgk.shape[0])
+                self._launch(L, C.c_void_p(packed.data_ptr() + lo * 28), C.cast(doff, C.c_void_p), k, hi - lo,
+                             C.c_void_p(tgk.data_ptr()) if ntk else C.c_void_p(0), ntk, tcols, C.cast(img5, C.c_void_p), dev, st)
+
+    @property
+    def matrix(self):
+        """(nc + 1, nc + 1) float64 numpy array [predicted][true], as the reference's attribute.  The one place that waits for
+        the device; raises RuntimeError when a class outside [0, nc) was met."""
+        cells = (self.nc + 1) ** 2
+        if self._mat is None:
+            return np.zeros((self.nc + 1, self.nc + 1))
+        torch.cuda.synchronize(self._mat.device)
+        host = self._mat.cpu().numpy()
+        if host[cells]:
+            raise RuntimeError(f"ConfusionMatrix: {int(host[cells])} cells were not counted: a detection or label class outside [0, {self.nc})")
+        return host[:cells].reshape(self.nc + 1, self.nc + 1).astype(np.float64)
+
+    def tp_fp(self):
+        matrix = self.matrix
+        tp = matrix.diagonal()  # true positives
+        fp = matrix.sum(1) - tp  # false positives
+        return tp[:-1], fp[:-1]  # remove background class
+
+    def plot(self, normalize=True, save_dir='', names=()):
+        raise NotImplementedError("ConfusionMatrix.plot: plots are not part of this package; assign this object's .matrix to the "
+                                  "reference's ConfusionMatrix and call its plot()")
+
+    def print(self):
+        matrix = self.matrix
+        for i in range(self.nc + 1):
+            print(' '.join(map(str, matrix[i])))

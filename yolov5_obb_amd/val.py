@@ -238,9 +238,11 @@ class ValStats:
         new[:used] = buf[:used]
         return new
 
-    def add_batch(self, preds, targets, shapes, iouv, want_boxes=False):
+    def add_batch(self, preds, targets, shapes, iouv, want_boxes=False, confusion=None):
         """The inputs of val_tail_batch; the rows go straight behind the ones already held.  Returns None, or with want_boxes
-        the packed device arrays (pred_poly, pred_hbb, pred_polyn, pred_hbbn) and the per-image offsets."""
+        the packed device arrays (pred_poly, pred_hbb, pred_polyn, pred_hbbn) and the per-image offsets.
+        confusion: a utils.metrics.ConfusionMatrix -- val.py:245-246 with plots=True: its launch runs right behind the tail's
+        two, on the same packed detections and targets."""
         import ctypes as C
         dev = self.device
         bs = len(preds)
@@ -303,6 +305,9 @@ class ValStats:
                     part(boxes[2], 10) if boxes else null, part(boxes[3], 6) if boxes else null,
                     part(self._rows, cols, self.n), C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(st))
                 _lib.check(rc, "obb_val_tail_batch_f32")
+                if confusion is not None:
+                    confusion._launch(L, part(packed, 7), C.cast(doff, C.c_void_p), k, hi - lo, C.c_void_p(tgk.data_ptr()) if ntk else null,
+                                      ntk, tcols, C.cast(img5, C.c_void_p), dev, st)
         self.n += n
         return (boxes, offs) if want_boxes else None
 

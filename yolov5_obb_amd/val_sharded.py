@@ -40,7 +40,8 @@ def _sync(device):
 
 
 def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True, single_cls=False, augment=False, device=None,
-        ap_per_class=None, names=None, nms=None, postprocess=None, match=None, niou=10, collect=True, device_metrics=False):
+        ap_per_class=None, names=None, nms=None, postprocess=None, match=None, niou=10, collect=True, device_metrics=False,
+        confusion_matrix=None):
     """The loop of val.py:180-250 over ``loader`` (this rank's shard, see shard_loader), then the gather.
 
     model(im) -> (out (b, A, no), train_out), like the reference's Model in eval mode.  ``loader`` yields
@@ -54,7 +55,10 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
     device_metrics=True (CUDA, one process, the HIP tail): the statistics stay in device memory (val.ValStats) and the metrics
     are this package's utils.metrics.ap_per_class over them -- ties among equal confidences by ascending row index, where the
     reference's numpy leaves them unspecified; `ap_per_class` is not called, "stats" stays None, "val_stats" is the accumulator
-    and "metrics" its 7-tuple, or None when nothing matched (val.py:270)."""
+    and "metrics" its 7-tuple, or None when nothing matched (val.py:270).
+    confusion_matrix (with device_metrics=True): a utils.metrics.ConfusionMatrix that every batch is added to on the device
+    (val.py:245-246 with plots=True); it comes back as "confusion_matrix".  One process only: its counters are plain sums that a
+    later change can all-reduce."""
     # the HIP path's tail runs once per BATCH (val.val_tail_batch: three launches, one copy); injected stand-ins keep the
     # reference's per-image loop
     batch_tail = None
@@ -81,6 +85,11 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
         if batch_tail is None or device.type != "cuda":
             raise RuntimeError("val_sharded.run: device_metrics=True needs a CUDA device and this package's own tail")
         vstats = V.ValStats(niou=niou, device=device)
+    if confusion_matrix is not None:
+        if world > 1:
+            raise RuntimeError("val_sharded.run: confusion_matrix needs a single process (world size 1)")
+        if vstats is None:
+            raise RuntimeError("val_sharded.run: confusion_matrix needs device_metrics=True")
     gidx = getattr(loader, "global_indices", None)
     per_image, dt, seen = [], [0.0, 0.0, 0.0], 0
     dt_batches = []                                                  # (pre-process, inference, NMS) seconds of every batch
@@ -106,7 +115,7 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
                     for pred in out:
                         pred[:, 6] = 0
                 if vstats is not None:
-                    vstats.add_batch(out, targets, shapes, iouv)                 # rows and label classes stay on the device
+                    vstats.add_batch(out, targets, shapes, iouv, confusion=confusion_matrix)      # rows and label classes stay on the device
                     seen += len(out)
                     continue
                 tail = batch_tail(out, targets, shapes, iouv)                    # val.py:209-250 for the whole batch
@@ -154,8 +163,11 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
                 "metrics": None, "dt_batches": dt_batches}
     if vstats is not None:
         metrics = vstats.ap_per_class()
-        return {"rank": rank, "world": world, "seen": seen, "dt": list(dt), "img_per_s": seen / max(sum(dt), 1e-12), "stats": None,
-                "metrics": metrics if vstats.any_tp else None, "dt_batches": dt_batches, "val_stats": vstats}
+        res = {"rank": rank, "world": world, "seen": seen, "dt": list(dt), "img_per_s": seen / max(sum(dt), 1e-12), "stats": None,
+               "metrics": metrics if vstats.any_tp else None, "dt_batches": dt_batches, "val_stats": vstats}
+        if confusion_matrix is not None:
+            res["confusion_matrix"] = confusion_matrix
+        return res
     # ---- the one exchange: per-image tuples to rank 0, in the original order of the image list
     if gidx is None:
         gidx = list(range(rank, rank + world * len(per_image), world)) if world > 1 else list(range(len(per_image)))
