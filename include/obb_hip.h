@@ -30,7 +30,7 @@ extern "C" {
 
 #define OBB_OK 0
 #define OBB_ERR_BAD_ARG (-1)
-#define OBB_ERR_WORKSPACE (-2)   /* ws == NULL or ws_bytes too small */
+#define OBB_ERR_WORKSPACE (-2)   /* ws (or state) == NULL, not 256-byte aligned, or ws_bytes (state_bytes) too small: answered before any device call */
 #define OBB_ERR_LAUNCH (-3)      /* a kernel launch failed (see hipGetLastError) */
 #define OBB_ERR_INTERNAL (-4)
 #define OBB_ERR_NO_DEVICE (-5)

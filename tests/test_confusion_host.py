@@ -20,9 +20,8 @@ from tests import confusion_cases as CC
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def hc(tmp_path_factory):
-    out = tmp_path_factory.mktemp("hc") / "libhostconfusion.so"
+def build_host_confusion(out):
+    """tests/native/host_confusion.cpp -> the shared library `out`, loaded with hc_confusion's signature set."""
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", f"-I{ROOT}/yolov5_obb_amd/csrc",
                     f"{ROOT}/tests/native/host_confusion.cpp", "-o", str(out), "-lm"], check=True)
     L = C.CDLL(str(out))
@@ -31,6 +30,11 @@ def hc(tmp_path_factory):
     L.hc_confusion.argtypes = [f32, C.c_long, f32, C.c_long, C.c_int, C.c_float, C.c_float, i64, C.c_int]
     L.hc_confusion.restype = C.c_int
     return L
+
+
+@pytest.fixture(scope="module")
+def hc(tmp_path_factory):
+    return build_host_confusion(tmp_path_factory.mktemp("hc") / "libhostconfusion.so")
 
 
 @pytest.fixture(scope="module")

@@ -819,7 +819,7 @@ static int val_tail_batch_impl(const float* det7, const int64_t* det_row_host, c
   const int64_t n = det_off_host[bs];
   if (n == 0) { if (done) *done = 0; return OBB_OK; }            // (host-visible memory: nothing to wait for)
   if (!det7 || !stats) return OBB_ERR_BAD_ARG;
-  if (!ws || ws_bytes < obb_val_tail_batch_workspace_bytes(n, nt)) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < obb_val_tail_batch_workspace_bytes(n, nt)) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   int* best_label = (int*)ws;
   float* best_iou = (float*)(best_label + n);
@@ -861,7 +861,7 @@ int obb_process_batch_f32(const float* det6, int64_t n, const float* lab5, int64
   if (n < 0 || m < 0 || niou < 1 || n > 0x7fffffff || m > 0x7fffffff) return OBB_ERR_BAD_ARG;
   if (n == 0) return OBB_OK;
   if (!det6 || !iouv || !correct || (m > 0 && !lab5)) return OBB_ERR_BAD_ARG;
-  if (!ws || ws_bytes < obb_process_batch_workspace_bytes(n, m)) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < obb_process_batch_workspace_bytes(n, m)) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   int* best_label = (int*)ws;
   float* best_iou = (float*)(best_label + n);
@@ -901,7 +901,7 @@ int obb_confusion_batch_f32(const float* det7, const int64_t* det_off_host, int6
   const int64_t n = det_off_host[bs];
   if (n == 0 || nt == 0) return OBB_OK;                          // no image has both detections and labels: nothing is counted
   if (!det7) return OBB_ERR_BAD_ARG;
-  if (!ws || ws_bytes < obb_confusion_workspace_bytes(n, nt)) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < obb_confusion_workspace_bytes(n, nt)) return OBB_ERR_WORKSPACE;
   obb::k_confusion<true><<<(unsigned)bs, obb::kCmThreads, 0, (hipStream_t)stream>>>(
       det7, im, 0, targets, (int)nt, (int)tcols, nc, conf_thres, iou_thres, reinterpret_cast<unsigned long long*>(matrix_i64), cm_carve(ws, n, nt));
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
@@ -912,7 +912,7 @@ int obb_confusion_process_batch_f32(const float* det6, int64_t n, const float* l
   if (n < 0 || m < 0 || n > 0x7fffffff || m > 0x7fffffff || nc < 1 || nc > 32767 || !matrix_i64) return OBB_ERR_BAD_ARG;
   if (n == 0 || m == 0) return OBB_OK;
   if (!det6 || !lab5) return OBB_ERR_BAD_ARG;
-  if (!ws || ws_bytes < obb_confusion_workspace_bytes(n, m)) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < obb_confusion_workspace_bytes(n, m)) return OBB_ERR_WORKSPACE;
   obb::ValTailImgs im = {};                                      // (not read by the one-image form)
   obb::k_confusion<false><<<1, obb::kCmThreads, 0, (hipStream_t)stream>>>(
       det6, im, (int)n, lab5, (int)m, 5, nc, conf_thres, iou_thres, reinterpret_cast<unsigned long long*>(matrix_i64), cm_carve(ws, n, m));

@@ -630,7 +630,7 @@ int obb_loss_build_targets(const obb_loss_config* cfg, const float* targets, int
   if ((nt > 0 && !targets) || (nt > 0 && tcols < 7) || !counts_out) return OBB_ERR_BAD_ARG;
   LossCarve cv;
   loss_carve(ws, cfg, nt, &cv);
-  if (!ws || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   LossDev d;
   loss_fill(d, cfg, cv, targets, nt, tcols);
@@ -649,7 +649,7 @@ int obb_loss_export_targets(const obb_loss_config* cfg, int64_t nt, int level, i
   if (!indices4 || !tbox4 || !anch2 || !tcls || !csl180) return OBB_ERR_BAD_ARG;
   LossCarve cv;
   loss_carve(ws, cfg, nt, &cv);
-  if (!ws || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
   k_bt_export<<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(cv.dev, level, (int)n, indices4, tbox4, anch2, tcls, csl180);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
@@ -662,7 +662,7 @@ int obb_loss_forward(const obb_loss_config* cfg, const void* const* p_levels_hos
     return OBB_ERR_BAD_ARG;
   LossCarve cv;
   loss_carve(ws, cfg, nt, &cv);
-  if (!ws || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   LossDev d;
   loss_fill(d, cfg, cv, targets, nt, tcols);
@@ -689,7 +689,7 @@ int obb_loss_backward(const obb_loss_config* cfg, const void* const* p_levels_ho
   if (!p_levels_host || !grad_levels_host || !grad_scale || (nt > 0 && !targets) || (dtype != 0 && dtype != 1)) return OBB_ERR_BAD_ARG;
   LossCarve cv;
   loss_carve(ws, cfg, nt, &cv);
-  if (!ws || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   LossDev d;
   loss_fill(d, cfg, cv, targets, nt, tcols);     // entries / counts / head in `ws` are the ones obb_loss_forward left there

@@ -449,7 +449,7 @@ int obb_ap_per_class_f32(const float* stats, int64_t row_stride, int64_t n, int 
   if (n < 0 || n >= 0x7fffffffLL || m < 0 || m >= 0x7fffffffLL || niou < 1 || niou > kApMaxIou || nc_max < 1 || nc_max > kApMaxNc)
     return OBB_ERR_BAD_ARG;
   if (!ap || !prf || !counts || !info || (n > 0 && (!stats || row_stride < niou + 2)) || (m > 0 && !target_cls)) return OBB_ERR_BAD_ARG;
-  if (!ws || ws_bytes < obb_ap_per_class_workspace_bytes(n, niou, nc_max)) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < obb_ap_per_class_workspace_bytes(n, niou, nc_max)) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const ApWs w = ap_layout((char*)ws, n, niou, nc_max);
   double* cur = curves ? curves : w.curves;

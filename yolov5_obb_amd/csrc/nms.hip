@@ -807,7 +807,7 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
   Carve cv;
   int rc = carve(ws, n, nseg, recq, C, &cv);
   if (rc) return rc;
-  if (!ws || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
   const int T = 256;
   const int drop_small = (flags & OBB_NMS_DROP_SMALL) ? 1 : 0;
   const unsigned gseg = 1;
@@ -946,7 +946,7 @@ static int run_merge_nms(int kind, const double* dets9, int stride, int64_t n, c
   Carve cv;
   int rc = carve(ws, n, nseg, kind_recq(kind), C, &cv);
   if (rc) return rc;
-  if (!ws || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
   const int T = 256;
   const unsigned gseg = (unsigned)((nseg + T - 1) / T);
   k_seg_from_offsets<<<gseg, T, 0, st>>>(seg_off, (int)nseg, cv.seg_begin, cv.seg_end, cv.keep_cnt);
@@ -976,7 +976,7 @@ static int run_nms_rot64(const double* dets5, const double* scores, int64_t n, f
   Carve cv;
   int rc = carve(ws, n, 1, RotGeom64::RECQ, C, &cv);
   if (rc) return rc;
-  if (!ws || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
   const int T = 256;
   if (n == 0) {
     if (hipMemsetAsync(cv.keep_cnt, 0, 4, st) != hipSuccess || hipMemsetAsync(cv.seg_begin, 0, 4, st) != hipSuccess) return OBB_ERR_LAUNCH;

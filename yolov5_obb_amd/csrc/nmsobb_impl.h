@@ -1409,7 +1409,7 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   ObbCarve cv;
   int rc = obb_carve(ws, bs, cap_img, ncs, &cv);
   if (rc) return rc;
-  if (!ws || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
   // caller-kept counters: zero when the call starts (the caller's memset, or the previous call's last kernel) -- no reset launch
   const bool kept = state != nullptr;
   if (kept) {
