@@ -35,6 +35,16 @@ extern "C" {
 #define OBB_ERR_INTERNAL (-4)
 #define OBB_ERR_NO_DEVICE (-5)
 
+/* Element type of a tensor handed over as `const void*` with a `dtype` argument (the Detect head's conv outputs, the prediction
+ * tensor built from them, the loss gradients): torch.float32, torch.float16 (val.py --half, model.half()) and torch.bfloat16
+ * (model.bfloat16(), torch.autocast(dtype=torch.bfloat16)).  Code 2 is RESERVED: it is refused like every other unknown code
+ * (OBB_ERR_BAD_ARG before any device call) and will not be given a meaning.  Where an entry's arithmetic "follows the input dtype",
+ * bf16 rounds float results to nearest even like c10::BFloat16 (a NaN becomes the quiet NaN 0x7FC0; finite values beyond the bf16
+ * range round to inf) -- csrc/bf16_bits.h. */
+#define OBB_DTYPE_F32 0
+#define OBB_DTYPE_F16 1
+#define OBB_DTYPE_BF16 3
+
 /* flags for obb_nms_rotated_* */
 #define OBB_NMS_DROP_SMALL 1 /* ignore boxes with min(w,h) < 0.001 (utils/nms_rotated/nms_rotated_wrapper.py:32-39) */
 
@@ -209,9 +219,9 @@ int64_t obb_task1_format_rows(const char* text_host, const int32_t* name_off_hos
  * multi-label expansion or best class, class filter, per-image top max_nms by confidence, class offset
  * (xy += cls*max_wh unless agnostic), obb_nms (incl. its min(w,h) < 0.001 filter), max_det truncation.
  *   pred        [bs][A][no] contiguous, no = 5 + nc + 180, rows [cx cy l s obj cls[nc] csl[180]] as produced by
- *               Detect's inference branch (models/yolo.py:67-81); dtype 0 = fp32, 1 = fp16 (val.py --half).
+ *               Detect's inference branch (models/yolo.py:67-81); dtype OBB_DTYPE_F32 / OBB_DTYPE_F16 (val.py --half) / OBB_DTYPE_BF16.
  *               The arithmetic follows the input dtype exactly like the reference (conf = obj*cls is rounded to
- *               fp16 for fp16 input, thresholds are compared in that dtype).
+ *               fp16 for fp16 input and to bf16 for bf16 input, thresholds are compared in that dtype).
  *   classes_host  optional HOST array of allowed class ids (n_classes entries; NULL = all)     (:834-835)
  *   extra8      optional device rows [img, x, y, l, s, theta, conf, cls] appended as candidates: the apriori
  *               `labels` of autolabelling (:807-813), prepared by the host layer; n_extra rows
@@ -306,7 +316,7 @@ int obb_non_max_suppression_obb_st(const void* pred, const void* objcol, int dty
 /* The same call fed straight from the Detect head's 1x1-conv outputs instead of `pred`: Detect.forward (models/yolo.py:61-81)
  * followed by non_max_suppression_obb (utils/general.py:772-862) as detect.py and val.py chain them, without the dense prediction
  * tensor z (bs, A, no) and the permuted raw head x in between.
- *   conv_out[l]  level l's conv output (bs, na*no, ny[l], nx[l]), contiguous, dtype 0 = fp32 / 1 = fp16; nl <= 4, na <=
+ *   conv_out[l]  level l's conv output (bs, na*no, ny[l], nx[l]), contiguous, dtype OBB_DTYPE_F32 / _F16 / _BF16; nl <= 4, na <=
  *                OBB_LOSS_MAX_ANCHORS, no = 5 + nc + 180 with 1 <= nc <= 256 (the limits of obb_detect_decode_levels and
  *                obb_non_max_suppression_obb)
  *   anchors_px_host HOST [nl][na][2] = Detect.anchors * stride, strides_host HOST [nl]: as obb_detect_decode_levels takes them
@@ -377,7 +387,8 @@ int obb_loss_export_targets(const obb_loss_config* cfg, int64_t nt, int level, i
                             float* anch2, int64_t* tcls, float* csl180, void* ws, size_t ws_bytes, void* stream);
 
 /* ComputeLoss.__call__ forward (utils/loss.py:122-192).  p_levels_host: HOST array of nl device pointers;
- * dtype 0 = fp32, 1 = fp16 (arithmetic is fp32 either way).  loss_out (device, 5 + nl floats):
+ * dtype OBB_DTYPE_F32 / _F16 / _BF16 (arithmetic is fp32 in every case; tobj is rounded to the head dtype as utils/loss.py:155
+ * does).  loss_out (device, 5 + nl floats):
  * [0] (lbox+lobj+lcls+ltheta)*bs, [1..4] lbox, lobj, lcls, ltheta (gains applied), [5+i] the un-balanced objectness
  * BCE of level i (what autobalance reads, :180-181).  [0] is NaN when a target row is out of range.
  * The workspace keeps the matched rows and (round 5) a dense copy of every anchor row's objectness logit for obb_loss_backward
@@ -395,7 +406,7 @@ int obb_loss_backward(const obb_loss_config* cfg, const void* const* p_levels_ho
 
 /*
  * Detect.forward, inference branch, for ONE level (models/yolo.py:61-79): conv_out is the 1x1-conv output
- * (bs, na*no, ny, nx), contiguous, dtype 0 = fp32 / 1 = fp16.  Writes (either pointer may be NULL)
+ * (bs, na*no, ny, nx), contiguous, dtype OBB_DTYPE_F32 / _F16 / _BF16.  Writes (either pointer may be NULL)
  *   x_perm_out  (bs, na, ny, nx, no)  the raw head, what `x[i].view(bs,na,no,ny,nx).permute(0,1,3,4,2).contiguous()` returns (:65)
  *   z_out       rows [a_offset, a_offset + na*ny*nx) of every image of the concatenated prediction tensor
  *               (bs, a_total, no): sigmoid, xy = (y*2-0.5+grid)*stride, wh = (y*2)^2*anchor_grid (:71-79),

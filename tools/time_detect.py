@@ -1,13 +1,23 @@
-"""Detect inference decode timing (development aid): bs 16, 1024^2, nc 15, conv outputs resident."""
+"""Detect inference decode timing (development aid): bs 16, 1024^2, nc 15, conv outputs resident.
+    python tools/time_detect.py [--dtype fp16,bf16,fp32] [--rounds N]
+The dtypes are timed one after the other, `rounds` times over (back-to-back columns of one process: the spread between rounds is
+the noise a difference between dtypes has to exceed)."""
+import argparse
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
 import torch
 from tests import synth
 from yolov5_obb_amd import _lib
+DTYPES = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
+ap = argparse.ArgumentParser()
+ap.add_argument("--dtype", default="fp16,fp32", help="comma list of fp32 / fp16 / bf16")
+ap.add_argument("--rounds", type=int, default=1)
+args = ap.parse_args()
 dev = torch.device("cuda:0")
 L = _lib.lib()
-for dtype, code in ((torch.float16, 1), (torch.float32, 0)):
+for dtype in [DTYPES[k] for k in args.dtype.split(",")] * args.rounds:
+    code = _lib.DTYPE_CODES[dtype]
     bs, na, nc = 16, 3, 15
     no = 5 + nc + 180
     sizes = (128, 64, 32)

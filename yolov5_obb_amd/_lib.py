@@ -236,6 +236,18 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+# the `dtype` argument of the entries that read the Detect head (include/obb_hip.h OBB_DTYPE_*; code 2 is reserved)
+DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 3}
+
+
+def dtype_code(t, who):
+    """OBB_DTYPE_* of a head tensor; any other dtype is an error (nothing is cast behind the caller's back)."""
+    code = DTYPE_CODES.get(t.dtype)
+    if code is None:
+        raise RuntimeError(f"{who}: float32, float16 or bfloat16 expected, got {t.dtype}")
+    return code
+
+
 def require_cuda(t, name):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor, got {type(t)}")

@@ -20,6 +20,15 @@ template <typename T> __device__ __forceinline__ float detect_sigmoid(float x) {
 template <> __device__ __forceinline__ float detect_sigmoid<__half>(float x) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
 }
+// bf16 tensors: the same hardware pair, deliberately.  The result is rounded to 8 significand bits right after, so the pair's
+// error (the product's rounding, 1 ulp of fp32 each for exp2 and the reciprocal: about 2^-22 relative in all) can only move
+// a result that sits within that distance of a bf16 rounding boundary, where the spacing is 2^-8 relative -- fewer than one
+// element in ten thousand, and then by one bf16 step, the freedom the reference's own libm has against a correctly rounded
+// sigmoid.  The correctly rounded expf and division of the fp32 path would buy nothing that survives the rounding
+// (tests/test_bf16_head_gpu.py caps the elements off the reference's rounding at 1 % and at one step).
+template <> __device__ __forceinline__ float detect_sigmoid<bf16_t>(float x) {
+  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
+}
 
 template <typename T>
 __device__ __forceinline__ float detect_decode_one(float raw, int ch, float gx, float gy, float stride, float aw, float ah) {

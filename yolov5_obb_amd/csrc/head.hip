@@ -39,6 +39,7 @@ struct DetectArgs {
 template <typename T> struct Pack16;                                   // 16 bytes of T
 template <> struct Pack16<float> { static constexpr int V = 4; };
 template <> struct Pack16<__half> { static constexpr int V = 8; };
+template <> struct Pack16<bf16_t> { static constexpr int V = 8; };
 
 // VEC: the input rows are 4-element aligned (HW % 4 == 0) and both outputs are 16-byte aligned at every tile start,
 // so the tile is read with 8/16-byte loads and written with 16-byte stores; otherwise element-wise accesses.
@@ -265,7 +266,7 @@ int obb_detect_decode_col(const void* conv_out, int dtype, int64_t bs, int64_t n
                           const float* anchors_px_host, float stride, void* x_perm_out, void* z_out, int64_t a_total,
                           int64_t a_offset, void* objcol_out, void* stream) {
   if (!conv_out || bs < 1 || na < 1 || na > OBB_LOSS_MAX_ANCHORS || no < 6 || no > 5 + 256 + 180 || ny < 1 || nx < 1 ||
-      (dtype != 0 && dtype != 1) || !anchors_px_host)
+      !dtype_known(dtype) || !anchors_px_host)
     return OBB_ERR_BAD_ARG;
   if (!x_perm_out && !z_out && !objcol_out) return OBB_OK;
   if ((z_out || objcol_out) && (a_offset < 0 || a_offset + na * ny * nx > a_total)) return OBB_ERR_BAD_ARG;
@@ -279,7 +280,7 @@ int obb_detect_decode_col(const void* conv_out, int dtype, int64_t bs, int64_t n
     d.anchor_px[a][1] = a < na ? anchors_px_host[a * 2 + 1] : 0.f;
   }
   const int HW = (int)(ny * nx);
-  const size_t esz = dtype == 0 ? 4 : 2;
+  const size_t esz = dtype_size(dtype);
   // 64-position tiles, 256 threads, 2-element skew, eight channel rows in flight per thread, non-temporal loads and stores
   // (every byte is touched once; a streaming store does not push the lines other workgroups are about to read out of L2).
   // Measured against it in round 3 on (16, 3*200, 128..32, ..) and removed: a 4-element skew with one LDS store per 4-position
@@ -306,7 +307,7 @@ int obb_detect_decode_col(const void* conv_out, int dtype, int64_t bs, int64_t n
   do {                                                                                                                              \
     if (vec) { OBB_LAUNCH_DETECT(T, true, 64, 256, 2, true); } else { OBB_LAUNCH_DETECT(T, false, 64, 256, 2); }                    \
   } while (0)
-  if (dtype == 0) OBB_LAUNCH_DETECT_T(float); else OBB_LAUNCH_DETECT_T(__half);
+  OBB_DISPATCH_DTYPE(dtype, T, OBB_LAUNCH_DETECT_T(T));
 #undef OBB_LAUNCH_DETECT_T
 #undef OBB_LAUNCH_DETECT
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
@@ -316,10 +317,10 @@ int obb_detect_decode_levels(int nl, const void* const* conv_out, int dtype, int
                              const int64_t* nx, const float* anchors_px_host, const float* strides_host, void* const* x_perm_out,
                              void* z_out, int64_t a_total, void* objcol_out, void* stream) {
   if (nl < 1 || nl > kDetectMaxLevels || !conv_out || !ny || !nx || !anchors_px_host || !strides_host || bs < 1 || na < 1 ||
-      na > OBB_LOSS_MAX_ANCHORS || no < 6 || no > 5 + 256 + 180 || (dtype != 0 && dtype != 1))
+      na > OBB_LOSS_MAX_ANCHORS || no < 6 || no > 5 + 256 + 180 || !dtype_known(dtype))
     return OBB_ERR_BAD_ARG;
   if (bs * na > 65535) return OBB_ERR_BAD_ARG;
-  const size_t esz = dtype == 0 ? 4 : 2;
+  const size_t esz = dtype_size(dtype);
   constexpr int tile_hw = 64, skew = 2;
   auto al16 = [](const void* p) { return p == nullptr || (((uintptr_t)p) & 15) == 0; };
   DetectLevels m;
@@ -360,8 +361,7 @@ int obb_detect_decode_levels(int nl, const void* const* conv_out, int dtype, int
       return OBB_ERR_LAUNCH;                                                                                                        \
     k_detect_decode_levels<T, VEC, tile_hw, 256, skew, NTS><<<grid, 256, lds, st>>>(m);                                             \
   } while (0)
-  if (dtype == 0) { if (vec) OBB_LAUNCH_LEVELS(float, true, true); else OBB_LAUNCH_LEVELS(float, false, false); }
-  else { if (vec) OBB_LAUNCH_LEVELS(__half, true, true); else OBB_LAUNCH_LEVELS(__half, false, false); }
+  OBB_DISPATCH_DTYPE(dtype, T, if (vec) OBB_LAUNCH_LEVELS(T, true, true); else OBB_LAUNCH_LEVELS(T, false, false));
 #undef OBB_LAUNCH_LEVELS
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }

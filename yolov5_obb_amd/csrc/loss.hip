@@ -395,6 +395,7 @@ __global__ __launch_bounds__(1024) void k_loss_finalize(const LossDev* __restric
 template <typename T> struct Vec16;
 template <> struct Vec16<float> { static constexpr int V = 4; };
 template <> struct Vec16<__half> { static constexpr int V = 8; };
+template <> struct Vec16<bf16_t> { static constexpr int V = 8; };
 
 typedef unsigned int loss_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -444,7 +445,7 @@ __global__ __launch_bounds__(256) void k_loss_bwd_dense(const LossDev* __restric
           } else {
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
             if (j >= 0) {
-              const uint32_t h = (uint32_t)__half_as_ushort(__float2half_rn(val)) << ((j & 1) * 16);
+              const uint32_t h = bits16_from_float<T>(val) << ((j & 1) * 16);
               const int q = j >> 1;
               if (q == 0) v.x = h; else if (q == 1) v.y = h; else if (q == 2) v.z = h; else v.w = h;
             }
@@ -658,7 +659,7 @@ int obb_loss_forward(const obb_loss_config* cfg, const void* const* p_levels_hos
                      int64_t tcols, float* loss_out, void* ws, size_t ws_bytes, void* stream) {
   int rc = loss_check(cfg, nt);
   if (rc) return rc;
-  if (!p_levels_host || !loss_out || (nt > 0 && !targets) || (nt > 0 && tcols < 7) || (dtype != 0 && dtype != 1))
+  if (!p_levels_host || !loss_out || (nt > 0 && !targets) || (nt > 0 && tcols < 7) || !dtype_known(dtype))
     return OBB_ERR_BAD_ARG;
   LossCarve cv;
   loss_carve(ws, cfg, nt, &cv);
@@ -671,12 +672,8 @@ int obb_loss_forward(const obb_loss_config* cfg, const void* const* p_levels_hos
   rc = run_match(cfg, cv, d, st);
   if (rc) return rc;
   dim3 gd(kDenseBlocks, cfg->nl);
-  if (dtype == 0) k_loss_dense_fwd<float><<<gd, 256, 0, st>>>(cv.dev);
-  else k_loss_dense_fwd<__half><<<gd, 256, 0, st>>>(cv.dev);
-  if (d.cap > 0) {
-    if (dtype == 0) k_loss_entries_fwd<float><<<entry_grid(d), 256, 0, st>>>(cv.dev);
-    else k_loss_entries_fwd<__half><<<entry_grid(d), 256, 0, st>>>(cv.dev);
-  }
+  OBB_DISPATCH_DTYPE(dtype, T, k_loss_dense_fwd<T><<<gd, 256, 0, st>>>(cv.dev));
+  if (d.cap > 0) OBB_DISPATCH_DTYPE(dtype, T, k_loss_entries_fwd<T><<<entry_grid(d), 256, 0, st>>>(cv.dev));
   k_loss_finalize<<<cfg->nl, 1024, 0, st>>>(cv.dev, cv.lvl_out, cv.counts + kLv + 1);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
@@ -686,7 +683,7 @@ int obb_loss_backward(const obb_loss_config* cfg, const void* const* p_levels_ho
                       void* stream) {
   int rc = loss_check(cfg, nt);
   if (rc) return rc;
-  if (!p_levels_host || !grad_levels_host || !grad_scale || (nt > 0 && !targets) || (dtype != 0 && dtype != 1)) return OBB_ERR_BAD_ARG;
+  if (!p_levels_host || !grad_levels_host || !grad_scale || (nt > 0 && !targets) || !dtype_known(dtype)) return OBB_ERR_BAD_ARG;
   LossCarve cv;
   loss_carve(ws, cfg, nt, &cv);
   if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
@@ -700,12 +697,8 @@ int obb_loss_backward(const obb_loss_config* cfg, const void* const* p_levels_ho
   }
   k_loss_setup<<<1, 256, 0, st>>>(d, cv.dev);
   dim3 gd(2048, cfg->nl);
-  if (dtype == 0) k_loss_bwd_dense<float><<<gd, 256, 0, st>>>(cv.dev);
-  else k_loss_bwd_dense<__half><<<gd, 256, 0, st>>>(cv.dev);
-  if (d.cap > 0) {
-    if (dtype == 0) k_loss_entries_bwd<float><<<entry_grid(d), 256, 0, st>>>(cv.dev);
-    else k_loss_entries_bwd<__half><<<entry_grid(d), 256, 0, st>>>(cv.dev);
-  }
+  OBB_DISPATCH_DTYPE(dtype, T, k_loss_bwd_dense<T><<<gd, 256, 0, st>>>(cv.dev));
+  if (d.cap > 0) OBB_DISPATCH_DTYPE(dtype, T, k_loss_entries_bwd<T><<<entry_grid(d), 256, 0, st>>>(cv.dev));
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 

@@ -1159,10 +1159,10 @@ int obb_non_max_suppression_obb_head(int nl, const void* const* conv_out, int dt
   // the limits of obb_detect_decode_levels and obb_non_max_suppression_obb, checked before anything is launched
   const int64_t nc = no - 5 - 180;
   if (nl < 1 || nl > kHeadMaxLevels || !conv_out || !ny || !nx || !anchors_px_host || !strides_host || bs < 1 || na < 1 ||
-      na > OBB_LOSS_MAX_ANCHORS || nc < 1 || nc > 256 || (dtype != 0 && dtype != 1) || bs * na > 65535)
+      na > OBB_LOSS_MAX_ANCHORS || nc < 1 || nc > 256 || !dtype_known(dtype) || bs * na > 65535)
     return OBB_ERR_BAD_ARG;
-  const int TP = dtype == 0 ? kHeadTile<float> : kHeadTile<__half>;
-  const size_t esz = dtype == 0 ? 4 : 2;
+  const size_t esz = dtype_size(dtype);
+  const int TP = 256 / (int)esz;                                  // kHeadTile<T> of the dtype's element type
   HeadFront h;
   h.nl = nl; h.na = (int)na; h.vec = 1;
   int64_t A = 0, tiles = 0;

@@ -24,7 +24,7 @@ constexpr int kHeadWaves = kHeadThreads / 64;
 constexpr int kHeadStage = 128;            // staged candidates per wave before a flush (k_decode's kDecStage)
 constexpr int kHeadPitchDw = 65;           // LDS pitch of a channel line: 256 bytes + one bank, so that the 16 lanes of a group
                                            // (16 consecutive channels of one position) hit 16 different banks
-template <typename T> constexpr int kHeadTile = 256 / (int)sizeof(T);   // positions per tile: one 256-byte line per channel
+template <typename T> constexpr int kHeadTile = 256 / (int)sizeof(T);   // positions per tile: one 256-byte line per channel (fp16 and bf16: 128)
 
 struct HeadFront {
   const void* in[kHeadMaxLevels];          // conv output of level l: (bs, na*no, ny, nx), contiguous
@@ -238,14 +238,14 @@ static int launch_decode_head(const HeadFront& h, const DecodeArgs& d, int dtype
   if (const int attr_dev = attr.need(); attr_dev != OncePerDevice::kDone) {
     const int lds = (int)head_lds_bytes(5 + 256 + 180);
     if (hipFuncSetAttribute((const void*)k_decode_head<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_decode_head<__half>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        hipFuncSetAttribute((const void*)k_decode_head<__half>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_decode_head<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
       return OBB_ERR_LAUNCH;
     attr.mark(attr_dev);
   }
   const dim3 grid((unsigned)h.tile_end[h.nl - 1], (unsigned)(d.bs * h.na));
   const size_t lds = head_lds_bytes(d.no);
-  if (dtype == 0) k_decode_head<float><<<grid, kHeadThreads, lds, st>>>(d, h);
-  else k_decode_head<__half><<<grid, kHeadThreads, lds, st>>>(d, h);
+  OBB_DISPATCH_DTYPE(dtype, T, k_decode_head<T><<<grid, kHeadThreads, lds, st>>>(d, h));
   return OBB_OK;
 }
 

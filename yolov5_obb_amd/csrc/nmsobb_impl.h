@@ -39,10 +39,13 @@ struct ClassMask { unsigned long long w[4]; int all; };   // allowed classes (nc
 template <typename T> __device__ __forceinline__ float mul_in_dtype(float a, float b);
 template <> __device__ __forceinline__ float mul_in_dtype<float>(float a, float b) { return a * b; }
 template <> __device__ __forceinline__ float mul_in_dtype<__half>(float a, float b) { return __half2float(__float2half_rn(a * b)); }
+// (bf16: two 8-bit significands give a 16-bit product, exact in fp32, so the one rounding below is torch's bf16 multiply bit for bit)
+template <> __device__ __forceinline__ float mul_in_dtype<bf16_t>(float a, float b) { return round_to_dtype<bf16_t>(a * b); }
 // python float threshold compared against a tensor of the input dtype: the scalar is cast to that dtype
 template <typename T> __device__ __forceinline__ float thr_in_dtype(float t);
 template <> __device__ __forceinline__ float thr_in_dtype<float>(float t) { return t; }
 template <> __device__ __forceinline__ float thr_in_dtype<__half>(float t) { return __half2float(__float2half_rn(t)); }
+template <> __device__ __forceinline__ float thr_in_dtype<bf16_t>(float t) { return round_to_dtype<bf16_t>(t); }
 
 // wave arg-max with "first maximum" tie rule (torch.max over a dimension: utils/general.py:822, :830).  Value and index
 // travel as ONE 64-bit key -- order-preserving image of the float in the high word (-0 counts as +0; every NaN, of either
@@ -1395,7 +1398,7 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   if (bs < 1 || A < 1 || nc < 1 || nc > 256 || max_det < 1 || cap_img < 1 || (!pred && !head) || !out || !out_count || !status)
     return OBB_ERR_BAD_ARG;
   if (A * nc + n_extra > 0xffffffffLL || bs * cap_img > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
-  if (dtype != 0 && dtype != 1) return OBB_ERR_BAD_ARG;
+  if (!dtype_known(dtype)) return OBB_ERR_BAD_ARG;
   // expected_cand: low 32 bits = the previous call's largest candidate count of an image (0: unknown), high 32 bits = its
   // largest NMS segment (0: unknown) -- both as status[1] reported them
   const int64_t seg_hint = (expected_cand >> 32) & 0x1fffffff;
@@ -1454,8 +1457,7 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
     if (head) {
       rc = launch_decode_head(*head, d, dtype, st);
       if (rc) return rc;
-    } else if (dtype == 0) k_decode<float><<<gd, kDecThreads, 0, st>>>(d);
-    else k_decode<__half><<<gd, kDecThreads, 0, st>>>(d);
+    } else OBB_DISPATCH_DTYPE(dtype, T, k_decode<T><<<gd, kDecThreads, 0, st>>>(d));
   }
   if (n_extra > 0 && extra8) k_append_extra<<<(unsigned)((n_extra + 255) / 256), 256, 0, st>>>(extra8, (int)n_extra, A, nc, d);
   if (small_hint && class_ok)

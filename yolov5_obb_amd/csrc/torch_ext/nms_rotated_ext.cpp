@@ -365,6 +365,14 @@ std::vector<at::Tensor> run_fused(const at::Device dev, int64_t bs, int64_t A, i
   return result;
 }
 
+// OBB_DTYPE_* of a head tensor (include/obb_hip.h)
+static int dtype_code(const at::Tensor& t) {
+  if (t.scalar_type() == at::kFloat) return OBB_DTYPE_F32;
+  if (t.scalar_type() == at::kHalf) return OBB_DTYPE_F16;
+  if (t.scalar_type() == at::kBFloat16) return OBB_DTYPE_BF16;
+  throw std::runtime_error(std::string("non_max_suppression_obb: float32, float16 or bfloat16 expected, got ") + c10::toString(t.scalar_type()));
+}
+
 std::vector<at::Tensor> non_max_suppression_obb(const at::Tensor& prediction, double conf_thres, double iou_thres,
                                                 const c10::optional<std::vector<int64_t>>& classes, bool agnostic, bool multi_label,
                                                 const c10::optional<at::Tensor>& extra, int64_t max_det,
@@ -374,10 +382,7 @@ std::vector<at::Tensor> non_max_suppression_obb(const at::Tensor& prediction, do
   if (prediction.dim() != 3) throw std::runtime_error("prediction must be (bs, anchors, no)");
   const int64_t nc = prediction.size(2) - 5 - kCsl;
   if (nc < 1 || nc > 256) throw std::runtime_error("non_max_suppression_obb: 1 <= nc <= 256 supported, got nc = " + std::to_string(nc));
-  int dtype;
-  if (prediction.scalar_type() == at::kFloat) dtype = 0;
-  else if (prediction.scalar_type() == at::kHalf) dtype = 1;
-  else throw std::runtime_error(std::string("non_max_suppression_obb: float32 or float16 expected, got ") + c10::toString(prediction.scalar_type()));
+  const int dtype = dtype_code(prediction);
   const at::Tensor pred = prediction.contiguous();
   const int64_t bs = pred.size(0), A = pred.size(1), no = pred.size(2);
   const at::Device dev = pred.device();
@@ -432,10 +437,7 @@ std::vector<at::Tensor> non_max_suppression_obb_head(const std::vector<at::Tenso
   if (c0.dim() != 4 || c0.size(1) % na != 0) throw std::runtime_error("non_max_suppression_obb_head: conv outputs (bs, na*no, ny, nx) expected");
   const int64_t bs = c0.size(0), no = c0.size(1) / na, nc = no - 5 - kCsl;
   if (nc < 1 || nc > 256) throw std::runtime_error("non_max_suppression_obb: 1 <= nc <= 256 supported, got nc = " + std::to_string(nc));
-  int dtype;
-  if (c0.scalar_type() == at::kFloat) dtype = 0;
-  else if (c0.scalar_type() == at::kHalf) dtype = 1;
-  else throw std::runtime_error(std::string("non_max_suppression_obb: float32 or float16 expected, got ") + c10::toString(c0.scalar_type()));
+  const int dtype = dtype_code(c0);
   const at::Device dev = c0.device();
   std::vector<const void*> ptrs;
   std::vector<int64_t> ny, nx;

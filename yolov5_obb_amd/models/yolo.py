@@ -106,12 +106,7 @@ class Detect(nn.Module):
             return type(self)._cpu_forward(self, x)
         convs = [self.m[i](x[i]).contiguous() for i in range(self.nl)]
         c0 = convs[0]
-        if c0.dtype == torch.float32:
-            code = 0
-        elif c0.dtype == torch.float16:
-            code = 1
-        else:
-            raise RuntimeError(f"Detect (inference): float32 or float16 expected, got {c0.dtype}")
+        code = _lib.dtype_code(c0, "Detect (inference)")       # fp32 / fp16 / bf16: the decode runs in the conv outputs' dtype
         anchor_px, strides = self._host_tables()
         bs = c0.shape[0]
         shapes = [(c.shape[2], c.shape[3]) for c in convs]

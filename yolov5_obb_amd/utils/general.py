@@ -125,7 +125,7 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
     """Runs Non-Maximum Suppression (NMS) on inference results_obb (utils/general.py:772-862).
 
     Args:
-        prediction (tensor): (b, n_all_anchors, [cx cy l s obj num_cls theta_cls]), fp32 or fp16, on the GPU
+        prediction (tensor): (b, n_all_anchors, [cx cy l s obj num_cls theta_cls]), fp32, fp16 or bf16, on the GPU
         agnostic (bool): True = NMS will be applied between elements of different categories
         labels : () or per-image apriori labels (n, [cls x y l s]) for autolabelling
     Returns:
@@ -148,12 +148,7 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
     assert 0 <= iou_thres <= 1, f'Invalid IoU {iou_thres}, valid values are between 0.0 and 1.0'
     if nc < 1 or nc > 256:
         raise RuntimeError(f"non_max_suppression_obb: 1 <= nc <= 256 supported, got nc = {nc}")
-    if prediction.dtype == torch.float32:
-        dtype = 0
-    elif prediction.dtype == torch.float16:
-        dtype = 1
-    else:
-        raise RuntimeError(f"non_max_suppression_obb: float32 or float16 expected, got {prediction.dtype}")
+    dtype = _lib.dtype_code(prediction, "non_max_suppression_obb")
     pred = prediction.contiguous()
     bs, A, no = pred.shape
     dev = pred.device

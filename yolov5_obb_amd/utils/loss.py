@@ -37,11 +37,7 @@ def _is_parallel(model):  # utils/torch_utils.py:215-217
 
 
 def _dtype_code(t):
-    if t.dtype == torch.float32:
-        return 0
-    if t.dtype == torch.float16:
-        return 1
-    raise RuntimeError(f"ComputeLoss: head outputs must be float32 or float16, got {t.dtype}")
+    return _lib.dtype_code(t, "ComputeLoss: head outputs")
 
 
 def _ptr_array(tensors):
