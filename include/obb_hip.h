@@ -431,6 +431,39 @@ int obb_detect_decode_levels(int nl, const void* const* conv_out, int dtype, int
                              const int64_t* nx, const float* anchors_px_host, const float* strides_host, void* const* x_perm_out,
                              void* z_out, int64_t a_total, void* objcol_out, void* stream);
 
+/* Augmented inference (models/yolo.py:149-209: _forward_augment, _descale_pred, _clip_augmented) behind the conv outputs of its
+ * passes, in ONE launch: every pass is decoded like obb_detect_decode_levels, its box channels 0..3 are de-scaled and de-flipped,
+ * and the rows land where torch.cat(_clip_augmented(y), 1) puts them -- pass after pass, level after level -- in z_out
+ * (bs, a_total, no), written once.  objcol_out (bs, a_total) or NULL receives z[..., 4] once more, bit-identical (the column of
+ * obb_non_max_suppression_obb_col).  The permuted raw heads are not written (train_out is None under augmentation).
+ *   A pass lists only the levels that SURVIVE the clip (the caller drops a clipped level by not listing it: its conv output is
+ *   never read); a clip that does not fall on a level boundary cannot be expressed -- use the eager chain there.
+ *   conv_out[l] (bs, na*no, ny[l], nx[l]) contiguous, dtype as below; anchors_px[l][a] = Detect.anchors * stride of that level;
+ *   scale  the pass's image scale (> 0, finite); flip 0 (none), 2 (up-down) or 3 (left-right), the dims of torch.flip;
+ *   img_h, img_w  the UN-scaled input size the de-flip mirrors at.
+ * Arithmetic per element, in the tensor dtype with the reference's rounding points: the decode as in obb_detect_decode, rounded;
+ * `/= scale` as torch evaluates it for a Python float -- a multiplication with (float)(1.0 / scale), the reciprocal taken once in
+ * double and then rounded to fp32 -- rounded
+ * (scale == 1 is the identity); flip 3: channel 0 = img_w - x, flip 2: channel 1 = img_h - y, in fp32, rounded.  Channels >= 4
+ * are the plain decode.  The result is bit-identical to the eager chain on the same device.
+ * Host structs, no workspace.  OBB_ERR_BAD_ARG before any device call for: npass outside 1..OBB_TTA_MAX_PASSES, a pass's nl outside
+ * 1..OBB_DETECT_MAX_LEVELS, a flip other than 0 / 2 / 3, a scale <= 0 or not finite, an image size < 1, a NULL z_out / passes /
+ * listed conv_out, na > OBB_LOSS_MAX_ANCHORS, no outside 6..441, an unknown dtype, a_total smaller than the rows listed. */
+#define OBB_TTA_MAX_PASSES 4
+#define OBB_DETECT_MAX_LEVELS 4
+typedef struct obb_tta_pass {
+  int32_t nl;                                                             /* surviving levels of this pass                  */
+  int32_t flip;                                                           /* 0, 2 (up-down) or 3 (left-right)               */
+  double scale;                                                           /* the Python float, unrounded                    */
+  int32_t img_h, img_w;                                                   /* the un-scaled input                            */
+  const void* conv_out[OBB_DETECT_MAX_LEVELS];                            /* DEVICE pointers                                */
+  int64_t ny[OBB_DETECT_MAX_LEVELS], nx[OBB_DETECT_MAX_LEVELS];
+  float stride[OBB_DETECT_MAX_LEVELS];
+  float anchors_px[OBB_DETECT_MAX_LEVELS][OBB_LOSS_MAX_ANCHORS][2];       /* pixels: Detect.anchors[l] * stride[l]          */
+} obb_tta_pass;
+int obb_detect_decode_tta(int npass, const obb_tta_pass* passes_host, int dtype, int64_t bs, int64_t na, int64_t no, void* z_out,
+                          int64_t a_total, void* objcol_out, void* stream);
+
 /* gaussian_label_cpu (utils/rboxs_utils.py:9-26) for n angles at once: out [n][num_class] fp32, evaluated in double. */
 int obb_csl_encode_f32(const float* labels, int64_t n, int num_class, double u, double sig, float* out, void* stream);
 

@@ -62,6 +62,7 @@ SIGNATURES = {
     "obb_detect_decode": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _vp, _f32, _vp, _vp, _i64, _i64, _vp]),
     "obb_detect_decode_col": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _vp, _f32, _vp, _vp, _i64, _i64, _vp, _vp]),
     "obb_detect_decode_levels": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "obb_detect_decode_tta": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),      # passes: TtaPass array (below)
     "obb_csl_encode_f32": (_i32, [_vp, _i64, _i32, C.c_double, C.c_double, _vp, _vp]),
     "obb_rbox2poly_f32": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "obb_val_postprocess_f32": (_i32, [_vp, _i64, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
@@ -83,6 +84,17 @@ SIGNATURES = {
     "_poly_nms": (None, [_vp, _vp, _vp, _i32, _i32, _f32, _i32]),
     "_overlaps": (None, [_vp, _vp, _vp, _i32, _i32, _i32]),
 }
+
+
+TTA_MAX_PASSES, DETECT_MAX_LEVELS, MAX_ANCHORS = 4, 4, 8       # OBB_TTA_MAX_PASSES, OBB_DETECT_MAX_LEVELS, OBB_LOSS_MAX_ANCHORS
+
+
+class TtaPass(C.Structure):
+    """obb_tta_pass of include/obb_hip.h (one pass of obb_detect_decode_tta)."""
+    _fields_ = [("nl", C.c_int32), ("flip", C.c_int32), ("scale", C.c_double), ("img_h", C.c_int32), ("img_w", C.c_int32),
+                ("conv_out", _vp * DETECT_MAX_LEVELS), ("ny", _i64 * DETECT_MAX_LEVELS),
+                ("nx", _i64 * DETECT_MAX_LEVELS), ("stride", _f32 * DETECT_MAX_LEVELS),
+                ("anchors_px", _f32 * 2 * MAX_ANCHORS * DETECT_MAX_LEVELS)]
 
 
 def lib():

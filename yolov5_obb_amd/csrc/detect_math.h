@@ -43,4 +43,18 @@ __device__ __forceinline__ float detect_decode_one(float raw, int ch, float gx, 
   return round_to_dtype<T>(q * (ch == 2 ? aw : ah));
 }
 
+// Augmented inference (models/yolo.py:183-198 _descale_pred, in-place branch) on a decoded box channel ch < 4, every step rounded
+// to the tensor dtype like the torch op it stands for:
+//   p[..., :4] /= scale          torch divides by a Python scalar as a multiplication with 1 / scale, the reciprocal taken once in
+//                                DOUBLE and rounded to fp32 (inv_scale, computed on the host; scale == 1 is the identity)
+//   p[..., 0] = img_w - p[..., 0]   flip 3 (left-right)          p[..., 1] = img_h - p[..., 1]   flip 2 (up-down)
+// the subtraction in fp32 on the integer image size.
+template <typename T>
+__device__ __forceinline__ float detect_descale_one(float v, int ch, float inv_scale, int flip, float img_w, float img_h) {
+  v = round_to_dtype<T>(v * inv_scale);
+  if (flip == 3 && ch == 0) v = round_to_dtype<T>(img_w - v);
+  if (flip == 2 && ch == 1) v = round_to_dtype<T>(img_h - v);
+  return v;
+}
+
 }  // namespace obb

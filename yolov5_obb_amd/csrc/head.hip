@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <cmath>
 #include <type_traits>
 #include "obb_hip.h"
 #include "dtype_device.h"
@@ -46,9 +47,18 @@ template <> struct Pack16<bf16_t> { static constexpr int V = 8; };
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 
+// what augmented inference does to the box channels of one pass after the decode (detect_descale_one, detect_math.h)
+struct DetectDescale {
+  float inv_scale;     // (float)(1.0 / scale), the division in double
+  int flip;            // 0 none, 2 up-down, 3 left-right (the dims torch.flip takes)
+  float img_w, img_h;  // size of the un-scaled input
+};
+
 // NTS: the tile is read and both outputs are written with non-temporal accesses (every byte is touched once)
-template <typename T, bool VEC, int kTileHW, int NT, int SK, bool NTS, bool NTL>
-__device__ __forceinline__ void detect_decode_tile(const DetectArgs& d, const int tile_x, const int ba /* b * na + a */) {
+// TTA: channels 0..3 go through detect_descale_one with *ds after the decode (the other instantiations do not look at ds)
+template <typename T, bool VEC, int kTileHW, int NT, int SK, bool NTS, bool NTL, bool TTA = false>
+__device__ __forceinline__ void detect_decode_tile(const DetectArgs& d, const int tile_x, const int ba /* b * na + a */,
+                                                   const DetectDescale* ds = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* tile = reinterpret_cast<T*>(smem_raw);            // [no] rows of 64 positions, skewed (tix)
   const int tid = threadIdx.x;
@@ -137,7 +147,9 @@ __device__ __forceinline__ void detect_decode_tile(const DetectArgs& d, const in
     if (c >= 4) return round_to_dtype<T>(detect_sigmoid<T>(r));      // 196 of the 200 channels: no grid arithmetic
     const int pos = hw0 + hw;
     const int gyi = pos / d.nx;
-    return detect_decode_one<T>(r, c, (float)(pos - gyi * d.nx), (float)gyi, d.stride, aw, ah);
+    const float v = detect_decode_one<T>(r, c, (float)(pos - gyi * d.nx), (float)gyi, d.stride, aw, ah);
+    if constexpr (TTA) return detect_descale_one<T>(v, c, ds->inv_scale, ds->flip, ds->img_w, ds->img_h);
+    else return v;
   };
   if constexpr (VEC) {
     constexpr int V = Pack16<T>::V;
@@ -201,6 +213,32 @@ __global__ __launch_bounds__(NT) void k_detect_decode_levels(DetectLevels m) {
   int l = 0;
   while (l + 1 < m.nl && bx >= m.tile_end[l]) l++;
   detect_decode_tile<T, VEC, kTileHW, NT, SK, NTS, NTS>(m.lv[l], bx - (l ? m.tile_end[l - 1] : 0), (int)blockIdx.y);
+}
+
+// Augmented inference (models/yolo.py:149-161 _forward_augment): the surviving levels of every pass in ONE launch, each an entry of
+// the table with the row offset its rows have in torch.cat(_clip_augmented(y), 1) and its pass's de-scale / de-flip.  blockIdx.x
+// runs over the tiles of entry 0, then entry 1, ...; blockIdx.y = b * na + a.  The vector path is chosen per entry (the conditions
+// of obb_detect_decode_levels, with the entry's own a_off): one odd level does not take it from the others.  Workgroup-uniform.
+constexpr int kTtaMaxEntries = OBB_TTA_MAX_PASSES * kDetectMaxLevels;
+struct TtaEntry {
+  DetectArgs d;
+  DetectDescale ds;
+  int vec;
+};
+struct TtaTable {
+  TtaEntry e[kTtaMaxEntries];
+  int tile_end[kTtaMaxEntries];                          // running sum of the entries' tile counts
+  int n;
+};
+template <typename T, int kTileHW, int NT, int SK>
+__global__ __launch_bounds__(NT) void k_detect_decode_tta(TtaTable m) {
+  const int bx = (int)blockIdx.x;
+  int l = 0;
+  while (l + 1 < m.n && bx >= m.tile_end[l]) l++;
+  const TtaEntry& e = m.e[l];
+  const int tx = bx - (l ? m.tile_end[l - 1] : 0);
+  if (e.vec) detect_decode_tile<T, true, kTileHW, NT, SK, true, true, true>(e.d, tx, (int)blockIdx.y, &e.ds);
+  else detect_decode_tile<T, false, kTileHW, NT, SK, false, false, true>(e.d, tx, (int)blockIdx.y, &e.ds);
 }
 
 // ------------------------------------------------------------------ CSL encode (utils/rboxs_utils.py:9-26)
@@ -363,6 +401,66 @@ int obb_detect_decode_levels(int nl, const void* const* conv_out, int dtype, int
   } while (0)
   OBB_DISPATCH_DTYPE(dtype, T, if (vec) OBB_LAUNCH_LEVELS(T, true, true); else OBB_LAUNCH_LEVELS(T, false, false));
 #undef OBB_LAUNCH_LEVELS
+  return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
+}
+
+int obb_detect_decode_tta(int npass, const obb_tta_pass* passes_host, int dtype, int64_t bs, int64_t na, int64_t no, void* z_out,
+                          int64_t a_total, void* objcol_out, void* stream) {
+  if (npass < 1 || npass > OBB_TTA_MAX_PASSES || !passes_host || !z_out || bs < 1 || na < 1 || na > OBB_LOSS_MAX_ANCHORS || no < 6 ||
+      no > 5 + 256 + 180 || !dtype_known(dtype) || a_total < 1)
+    return OBB_ERR_BAD_ARG;
+  if (bs * na > 65535) return OBB_ERR_BAD_ARG;
+  const size_t esz = dtype_size(dtype);
+  constexpr int tile_hw = 64, skew = 2;
+  auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+  // rows of image b start at b * a_total: 16-byte aligned for every b (or there is no b > 0)
+  const bool vec_all = al16(z_out) && (bs == 1 || ((size_t)a_total * no * esz) % 16 == 0);
+  TtaTable m;
+  int n = 0;
+  int64_t off = 0, tiles = 0;
+  for (int p = 0; p < npass; p++) {
+    const obb_tta_pass& ps = passes_host[p];
+    if (ps.nl < 1 || ps.nl > kDetectMaxLevels || (ps.flip != 0 && ps.flip != 2 && ps.flip != 3) || !(ps.scale > 0.0) ||
+        !std::isfinite(ps.scale) || ps.img_h < 1 || ps.img_w < 1)
+      return OBB_ERR_BAD_ARG;
+    for (int l = 0; l < ps.nl; l++) {
+      if (!ps.conv_out[l] || ps.ny[l] < 1 || ps.nx[l] < 1 || ps.ny[l] * ps.nx[l] > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
+      TtaEntry& e = m.e[n];
+      DetectArgs& d = e.d;
+      d.in = ps.conv_out[l]; d.xperm = nullptr; d.z = z_out; d.objcol = objcol_out;
+      d.bs = (int)bs; d.na = (int)na; d.no = (int)no; d.ny = (int)ps.ny[l]; d.nx = (int)ps.nx[l];
+      d.a_total = a_total; d.a_off = off; d.stride = ps.stride[l];
+      for (int a = 0; a < OBB_LOSS_MAX_ANCHORS; a++) {
+        d.anchor_px[a][0] = a < na ? ps.anchors_px[l][a][0] : 0.f;
+        d.anchor_px[a][1] = a < na ? ps.anchors_px[l][a][1] : 0.f;
+      }
+      e.ds.inv_scale = (float)(1.0 / ps.scale);           // what torch's `/= python_float` multiplies with (detect_math.h)
+      e.ds.flip = ps.flip; e.ds.img_w = (float)ps.img_w; e.ds.img_h = (float)ps.img_h;
+      const int64_t HW = ps.ny[l] * ps.nx[l];
+      e.vec = vec_all && (HW % 4 == 0) && al16(ps.conv_out[l]) && ((size_t)HW * no * esz) % 16 == 0 && ((size_t)off * no * esz) % 16 == 0;
+      tiles += (HW + tile_hw - 1) / tile_hw;
+      if (tiles > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
+      m.tile_end[n] = (int)tiles;
+      off += na * HW;
+      if (off > a_total) return OBB_ERR_BAD_ARG;          // more rows listed than z_out has
+      n++;
+    }
+  }
+  m.n = n;
+  for (int k = n; k < kTtaMaxEntries; k++) { m.e[k] = m.e[0]; m.tile_end[k] = (int)tiles; }
+  const size_t lds = ((size_t)no * tile_hw + (size_t)skew * (size_t)(no / 8 + 2)) * esz;
+  if (lds > 150 * 1024) return OBB_ERR_BAD_ARG;
+  dim3 grid((unsigned)tiles, (unsigned)(bs * na));
+  hipStream_t st = (hipStream_t)stream;
+#define OBB_LAUNCH_TTA(T)                                                                                                           \
+  do {                                                                                                                              \
+    if (lds > 48 * 1024 &&                                                                                                          \
+        hipFuncSetAttribute((const void*)k_detect_decode_tta<T, tile_hw, 256, skew>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
+      return OBB_ERR_LAUNCH;                                                                                                        \
+    k_detect_decode_tta<T, tile_hw, 256, skew><<<grid, 256, lds, st>>>(m);                                                          \
+  } while (0)
+  OBB_DISPATCH_DTYPE(dtype, T, OBB_LAUNCH_TTA(T));
+#undef OBB_LAUNCH_TTA
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 

@@ -10,6 +10,8 @@ What it does (INTEGRATION.md section 1 as code):
   * imports the reference's `utils.general`, `utils.loss`, `utils.rboxs_utils`, `models.yolo` and replaces, in those
     modules, the hot-path objects by this package's (`non_max_suppression_obb`, `ComputeLoss`, `Detect`, `rbox2poly`,
     `poly2hbb`) -- scripts imported afterwards bind the replacements (`from utils.general import non_max_suppression_obb`);
+  * wraps `models.yolo.Model._forward_augment` (`val.py --augment`): with `Detect.fused_tta` set and a GPU tensor the three passes
+    end in one `obb_detect_decode_tta` launch (`models.yolo.forward_augment` of this package); otherwise the reference's method;
   * `uninstall()` puts everything back.
 Nothing of the reference is copied or modified on disk.
 
@@ -138,6 +140,16 @@ def install(patch_loaded_scripts=True, reference_cpu_ext=None):
     # checkout of the reference resolves to its own class (same constructor, attributes and parameter names)
     _set_attr(my_yolo.Detect, "__module__", "models.yolo")
     _set_attr(yolo, "Detect", my_yolo.Detect)           # parse_model resolves layer names in models.yolo's namespace
+    # augmented inference (`val.py --augment`): with Detect.fused_tta on GPU tensors the three passes end in ONE decode launch
+    # (models.yolo.forward_augment of this package, resizing with the reference's own scale_img); otherwise the reference's method
+    ref_augment = yolo.Model._forward_augment
+
+    def _forward_augment(self, x):
+        if getattr(self.model[-1], "fused_tta", False) and _is_cuda(x):
+            return my_yolo.forward_augment(self, x, scale_img=yolo.scale_img)
+        return ref_augment(self, x)
+
+    _set_attr(yolo.Model, "_forward_augment", _forward_augment)
     # 3. scripts that were imported before install(): rebind the names they copied
     if patch_loaded_scripts:
         for script in ("val", "detect", "train"):

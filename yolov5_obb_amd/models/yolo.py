@@ -12,11 +12,18 @@ more as a dense (bs, A) tensor and hangs it on the returned ``z`` (``z._obb_objc
 ``utils.general.non_max_suppression_obb`` reads its confidence filter from that column -- 2 bytes per anchor instead of one
 128-byte line of every 400-byte row -- when it is handed this very tensor object, unmodified (same ``_version``); any other
 tensor (a clone, a cast, the TTA concatenation, an in-place edit) takes the plain path.  The results are identical.
+
+Augmented inference (``Model._forward_augment``, :149-209): ``forward_augment`` below.  With ``Detect.fused_tta`` the three passes'
+conv outputs are decoded, de-scaled, de-flipped and laid out like ``torch.cat(_clip_augmented(y), 1)`` by ONE launch of
+``obb_detect_decode_tta``, and the result keeps its objectness column (the concatenation of the eager chain loses it).
 """
+import collections
 import ctypes as C
+import math
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import _lib
 from ..lazy import LazyTensor
@@ -40,6 +47,10 @@ class Detect(nn.Module):
     # return z and x as lazy tensors (yolov5_obb_amd/lazy.py) that non_max_suppression_obb reads straight from the conv outputs
     # (obb_non_max_suppression_obb_head): nothing of size (bs, A, no) is written unless something else touches them
     lazy_nms = False
+    # augmented inference (forward_augment below, Model._forward_augment under dropin.install()): the three passes' surviving
+    # levels decoded, de-scaled, de-flipped and concatenated by ONE launch of obb_detect_decode_tta.  Opt-in like lazy_nms.
+    fused_tta = False
+    _collect = False         # set by forward_augment around its passes: forward() returns the conv outputs
 
     def __init__(self, nc=80, anchors=(), ch=(), inplace=True):  # detection layer
         super().__init__()
@@ -105,13 +116,19 @@ class Detect(nn.Module):
                                    "under yolov5_obb_amd.dropin.install() CPU tensors run the reference's own Detect.forward")
             return type(self)._cpu_forward(self, x)
         convs = [self.m[i](x[i]).contiguous() for i in range(self.nl)]
+        if self._collect:      # forward_augment: the conv outputs of this pass, nothing launched here
+            return convs
+        return self._decode(convs, x)
+
+    def _decode(self, convs, x, allow_lazy=True):
+        """The inference branch behind the 1x1 convs: (z, x) with x[i] replaced by the permuted raw heads."""
         c0 = convs[0]
         code = _lib.dtype_code(c0, "Detect (inference)")       # fp32 / fp16 / bf16: the decode runs in the conv outputs' dtype
         anchor_px, strides = self._host_tables()
         bs = c0.shape[0]
         shapes = [(c.shape[2], c.shape[3]) for c in convs]
         a_total = sum(self.na * ny * nx for ny, nx in shapes)
-        if self._lazy_possible(convs):
+        if allow_lazy and self._lazy_possible(convs):
             for i, (ny, nx) in enumerate(shapes):
                 if self.onnx_dynamic or self.grid[i].shape[2:4] != (ny, nx):
                     self.grid[i], self.anchor_grid[i] = self._make_grid(nx, ny, i)
@@ -231,3 +248,143 @@ def _lazy_outputs(convs, code, na, no, anchor_px, strides, a_total, x):
     for i, c in enumerate(convs):
         x[i] = LazyTensor((bs, na, c.shape[2], c.shape[3], no), dt, dev, make_x(i))
     return z, x
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Augmented inference (models/yolo.py:149-209 of the reference: _forward_augment, _descale_pred, _clip_augmented)
+
+TtaPassPlan = collections.namedtuple("TtaPassPlan", "levels offsets rows lo hi")
+TtaPlan = collections.namedtuple("TtaPlan", "passes a_total on_boundary")
+
+
+def _clip_rows(totals, nl):
+    """The row range [lo, hi) every pass keeps of its `totals[k]` rows (the row-count rule of tta_plan's docstring)."""
+    g = sum(4 ** k for k in range(nl))
+    lo, hi = [0] * len(totals), list(totals)
+    cut = hi[0] // g
+    hi[0] = hi[0] - cut if cut else 0                      # a slice [:-0] keeps nothing
+    cut = ((hi[-1] - lo[-1]) // g) * 4 ** (nl - 1)
+    lo[-1] = min(lo[-1] + cut, hi[-1])
+    return lo, hi
+
+
+def tta_plan(level_shapes_per_pass, na, nl):
+    """Where the rows of every pass land in torch.cat(_clip_augmented(y), 1).  Pure Python.
+
+    level_shapes_per_pass: per pass, the (ny, nx) of its nl levels.  The reference clips by ROW COUNT (models/yolo.py:200-209):
+    with g = sum(4**k for k < nl), the first pass loses its last (A0 // g) * 1 rows and the last pass its first
+    (A_last // g) * 4**(nl - 1) rows -- whole levels exactly when the levels' areas are in the ratio 4:1.
+
+    Returns TtaPlan(passes, a_total, on_boundary); per pass TtaPassPlan(levels, offsets, rows, lo, hi): the kept row range
+    [lo, hi) of the pass's own rows, `rows` = hi - lo, the levels that lie inside it and the output row each of them starts at.
+    on_boundary is False when a cut splits a level (`levels` then lists only the whole ones: the plan cannot be decoded level-wise).
+    """
+    rows = [[na * ny * nx for ny, nx in shapes] for shapes in level_shapes_per_pass]
+    lo, hi = _clip_rows([sum(r) for r in rows], nl)
+    passes, out, on_boundary = [], 0, True
+    for r, a, b in zip(rows, lo, hi):
+        edges = [sum(r[:k]) for k in range(len(r) + 1)]
+        if b > a and not (a in edges and b in edges):
+            on_boundary = False
+        levels, offsets = [], []
+        for k in range(len(r)):
+            if r[k] and edges[k] >= a and edges[k + 1] <= b:
+                levels.append(k)
+                offsets.append(out + edges[k] - a)
+        passes.append(TtaPassPlan(tuple(levels), tuple(offsets), b - a, a, b))
+        out += b - a
+    return TtaPlan(passes, out, on_boundary)
+
+
+def scale_img(img, ratio=1.0, same_shape=False, gs=32):
+    """An image batch (bs, c, h, w) resized by `ratio` (bilinear, align_corners=False) and padded with 0.447 up to the next
+    multiple of gs of the scaled size -- or back to (h, w) with same_shape.  Ratio 1 returns the batch itself.  Same values as
+    the reference's utils.torch_utils.scale_img."""
+    if ratio == 1.0:
+        return img
+    h, w = img.shape[2:]
+    nh, nw = int(h * ratio), int(w * ratio)
+    out = F.interpolate(img, size=(nh, nw), mode="bilinear", align_corners=False)
+    ph, pw = (h, w) if same_shape else (math.ceil(h * ratio / gs) * gs, math.ceil(w * ratio / gs) * gs)
+    return F.pad(out, [0, pw - nw, 0, ph - nh], value=0.447)
+
+
+_scale_img = scale_img       # (forward_augment has a parameter of that name)
+
+
+def _decode_tta(det, convs_per_pass, plan, scales, flips, img_h, img_w):
+    """One obb_detect_decode_tta launch for the plan's surviving levels -> z (bs, a_total, no) with the objectness column."""
+    c0 = convs_per_pass[0][0]
+    code = _lib.dtype_code(c0, "forward_augment")
+    anchor_px, strides = det._host_tables()
+    bs, na = c0.shape[0], det.na
+    listed = [(k, p) for k, p in enumerate(plan.passes) if p.levels]
+    arr = (_lib.TtaPass * len(listed))()
+    for t, (k, p) in zip(arr, listed):
+        t.nl, t.flip, t.scale, t.img_h, t.img_w = len(p.levels), int(flips[k] or 0), float(scales[k]), int(img_h), int(img_w)
+        for j, lv in enumerate(p.levels):
+            c = convs_per_pass[k][lv]
+            t.conv_out[j], t.ny[j], t.nx[j], t.stride[j] = c.data_ptr(), c.shape[2], c.shape[3], strides[lv]
+            for a in range(na):
+                t.anchors_px[j][a][0], t.anchors_px[j][a][1] = anchor_px[lv][2 * a], anchor_px[lv][2 * a + 1]
+    z = torch.empty((bs, plan.a_total, det.no), dtype=c0.dtype, device=c0.device)
+    col = torch.empty((bs, plan.a_total), dtype=c0.dtype, device=c0.device) if det.couple_nms else None
+    with torch.cuda.device(c0.device):
+        rc = _lib.lib().obb_detect_decode_tta(len(listed), C.cast(arr, C.c_void_p), code, bs, na, det.no, _lib.ptr(z), plan.a_total,
+                                              _lib.ptr(col), _lib.stream_ptr(c0.device))
+    _lib.check(rc, "obb_detect_decode_tta")
+    if col is not None and not torch.is_inference(z):      # as in Detect.forward: no version counter, no column
+        z._obb_objcol = (col, z._version)
+    return z
+
+
+def forward_augment(model, x, scales=(1, 0.83, 0.67), flips=(None, 3, None), scale_img=None):
+    """Model._forward_augment of the reference for a model whose head is this package's Detect: (z, None).
+
+    With Detect.fused_tta on GPU tensors the passes run with the head collecting its conv outputs, and ONE launch decodes,
+    de-scales, de-flips and concatenates them (obb_detect_decode_tta): z is written once, in place, with the objectness column
+    attached.  fused_tta wins over lazy_nms here.  Otherwise -- fused_tta off, CPU tensors, nl > 4, a flip other than None / 2 / 3,
+    or a clip that does not fall on a level boundary (tta_plan) -- the reference's chain of torch ops on the eager passes; the
+    values are the same.  scale_img: the reference's utils.torch_utils.scale_img, or None for this module's.
+    """
+    det = model.model[-1]
+    resize = scale_img or _scale_img
+    gs = int(torch.as_tensor(model.stride).max())
+    img_h, img_w = x.shape[-2:]
+    passes = list(zip(scales, flips))
+
+    def run(si, fi):
+        return model._forward_once(resize(x.flip(fi) if fi else x, si, gs=gs))
+
+    fused = (getattr(det, "fused_tta", False) and x.is_cuda and not det.training and det.nl <= _lib.DETECT_MAX_LEVELS
+             and det.na <= _lib.MAX_ANCHORS and 1 <= len(passes) <= _lib.TTA_MAX_PASSES and all(fi in (None, 0, 2, 3) for _, fi in passes)
+             and all(si > 0 and math.isfinite(si) for si, _ in passes))
+    if fused:
+        det._collect = True
+        try:
+            convs = [run(si, fi) for si, fi in passes]
+        finally:
+            del det._collect
+        plan = tta_plan([[tuple(c.shape[2:]) for c in cs] for cs in convs], det.na, det.nl)
+        if plan.on_boundary and plan.a_total > 0:
+            return _decode_tta(det, convs, plan, [s for s, _ in passes], [f for _, f in passes], img_h, img_w), None
+        y = [det._decode(cs, list(cs), allow_lazy=False)[0] for cs in convs]     # the cut splits a level: the chain, eagerly
+    else:
+        y = [run(si, fi)[0] for si, fi in passes]
+    return _augment_chain(y, passes, img_h, img_w, det.nl, getattr(model, "inplace", True)), None
+
+
+def _augment_chain(y, passes, img_h, img_w, nl, inplace=True):
+    """_descale_pred, _clip_augmented and the torch.cat of the reference on the passes' predictions (torch ops)."""
+    out = []
+    for p, (si, fi) in zip(y, passes):
+        if not inplace:
+            p = p.clone()
+        p[..., :4] /= si
+        if fi == 2:
+            p[..., 1] = img_h - p[..., 1]
+        elif fi == 3:
+            p[..., 0] = img_w - p[..., 0]
+        out.append(p)
+    lo, hi = _clip_rows([p.shape[1] for p in out], nl)
+    return torch.cat([p[:, a:b] for p, a, b in zip(out, lo, hi)], 1)
