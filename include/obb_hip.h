@@ -391,6 +391,10 @@ int obb_loss_export_targets(const obb_loss_config* cfg, int64_t nt, int level, i
  * does).  loss_out (device, 5 + nl floats):
  * [0] (lbox+lobj+lcls+ltheta)*bs, [1..4] lbox, lobj, lcls, ltheta (gains applied), [5+i] the un-balanced objectness
  * BCE of level i (what autobalance reads, :180-181).  [0] is NaN when a target row is out of range.
+ * Non-finite logits are data: the loss, each item and every gradient element are finite exactly where the reference's are
+ * (inf and NaN are not told apart: an infinite objectness logit of a matched cell gives NaN where the reference gives inf).
+ * A NaN box logit of a matched cell reaches lbox and, through the cell's objectness target iou.detach().clamp(0) (torch's
+ * clamp propagates NaN, argsort under sort_obj_iou ranks it last), lobj and the gradients of the cell's channels 0..4.
  * The workspace keeps the matched rows and (round 5) a dense copy of every anchor row's objectness logit for obb_loss_backward
  * (which then reads 4 contiguous bytes per row instead of one 128-byte line of each 800-byte row): pass the same buffer, untouched. */
 int obb_loss_forward(const obb_loss_config* cfg, const void* const* p_levels_host, int dtype, const float* targets, int64_t nt,

@@ -97,3 +97,78 @@ def test_focal_bce_forward_and_gradient(hl, pw, gamma):
     hl.hc_focal(np.ascontiguousarray(torch.stack((x.detach(), t), 1).numpy()), n, pw, gamma, out)
     assert abs(out[:, 0].astype(np.float64).sum() - float(loss)) <= 1e-5 * abs(float(loss))
     assert np.allclose(out[:, 1], x.grad.numpy(), rtol=2e-5, atol=2e-6), np.abs(out[:, 1] - x.grad.numpy()).max()
+
+
+# ----------------------------------------------------------------------------- saturation grid
+# The tests above stay inside |x| < 30 with atol 1e-6, which is larger than anything that happens beyond |x| = 16.  A trained
+# head's background sits at -5..-12, peaks and fp16 overflow go to +-inf: the grid below walks through the points where
+# sigmoid, 1 - sigmoid and exp(-|x|) leave the fp32 range one after the other (16-17: 1 - sigmoid(x) becomes 0 / 1; 88.8:
+# expf overflows; 104: expf(-x) becomes 0 past the subnormals).
+SAT_X = [0.0] + [s * v for v in (4.6, 8, 12, 16, 17, 20, 30, 50, 88.8, 100, 104, 200, 1e30, float("inf")) for s in (1, -1)] \
+    + [float("nan")]
+SAT_T = [0.0, 0.3, 0.95, 1.0]
+SAT_RTOL, SAT_ATOL = 1e-5, 1.2e-7         # one fp32 ulp of 1: the size of the 1 - sigmoid cancellation in bce_logits_grad
+
+
+def _torch_focal(x, t, pw, gamma):
+    """(element losses, d sum / dx) of torch fp32: BCEWithLogits(pos_weight), wrapped in FocalLoss when gamma > 0."""
+    x = x.clone().requires_grad_(True)
+    pwt = torch.tensor([pw])
+    if gamma > 0:
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(x, t, pos_weight=pwt, reduction='none')
+        p = torch.sigmoid(x)
+        p_t = t * p + (1 - t) * (1 - p)
+        loss = loss * (t * 0.25 + (1 - t) * 0.75) * (1.0 - p_t) ** gamma          # utils/loss.py:35-62, as pyref.focal_bce
+    else:
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(x, t, pos_weight=pwt, reduction='none')
+    loss.sum().backward()
+    return loss.detach().numpy(), x.grad.numpy()
+
+
+def saturation_grid_mismatches(lib, pw, gamma):
+    """[(what, x, t, ours, torch)] over SAT_X x SAT_T: an isfinite pattern that differs from torch fp32, or a finite value
+    outside SAT_RTOL * |torch| + SAT_ATOL.  inf against NaN is a pattern match: both are non-finite."""
+    x = torch.tensor([xv for xv in SAT_X for _ in SAT_T], dtype=torch.float32)
+    t = torch.tensor([tv for _ in SAT_X for tv in SAT_T], dtype=torch.float32)
+    want = _torch_focal(x, t, pw, gamma)
+    out = np.zeros((len(x), 2), np.float32)
+    lib.hc_focal(np.ascontiguousarray(torch.stack((x, t), 1).numpy()), len(x), pw, gamma, out)
+    bad = []
+    for k, what in enumerate(("loss", "grad")):
+        got, ref = out[:, k], want[k]
+        fin = np.isfinite(ref)
+        for i in np.nonzero(np.isfinite(got) != fin)[0]:
+            bad.append((what + " isfinite", float(x[i]), float(t[i]), float(got[i]), float(ref[i])))
+        both = fin & np.isfinite(got)
+        err = np.abs(got[both].astype(np.float64) - ref[both])
+        for i in np.nonzero(both)[0][err > SAT_RTOL * np.abs(ref[both]) + SAT_ATOL]:
+            bad.append((what, float(x[i]), float(t[i]), float(got[i]), float(ref[i])))
+    return bad, out, want
+
+
+SAT_CONFIGS = [(1.0, 0.0), (2.5, 0.0), (1.0, 1.5), (1.0, 2.0), (1.0, 0.5)]
+
+
+@pytest.mark.parametrize("pw,gamma", SAT_CONFIGS)
+def test_saturation_grid(hl, pw, gamma):
+    """bce_logits / bce_focal and their gradients where the logits saturate, overflow or are not finite, against torch fp32:
+    the same isfinite pattern and, where finite, |k - torch| <= 1e-5 |torch| + 1.2e-7 (measured: the largest absolute gap is
+    2e-8, at x = -17, t = 0, where the header's (1-t) - lw (1 - sigmoid) is exactly 0 and ATen's sigmoid - t keeps 4e-8).
+    gamma = 0.5 gives NaN gradients at |x| >= 17 in torch and in the header alike ((1 - p_t)^(gamma - 1) at 0)."""
+    bad, out, want = saturation_grid_mismatches(hl, pw, gamma)
+    fin = np.isfinite(want[1]) & np.isfinite(out[:, 1])
+    print(f"saturation grid pw {pw} gamma {gamma}: largest |grad - torch| {np.abs(out[fin, 1] - want[1][fin]).max():.1e}, "
+          f"non-finite losses {int((~np.isfinite(want[0])).sum())}, gradients {int((~np.isfinite(want[1])).sum())} of {len(out)}")
+    assert not bad, bad[:8]
+    if gamma == 0.5:
+        assert (~np.isfinite(want[1])).sum() > (~np.isfinite(want[0])).sum()       # NaN gradients next to finite losses
+
+
+def test_bce_gradient_does_not_lose_the_background(hl):
+    """t = 0, x in [-16, -5] (background objectness): the header's gradient (1-t) - lw (1 - sigmoid(x)) against sigmoid(x) in
+    double stays within one fp32 ulp of 1 absolute -- the cancellation's size -- and is never negative."""
+    x = torch.linspace(-16.0, -5.0, 4401)
+    out = np.zeros((len(x), 2), np.float32)
+    hl.hc_bce(np.ascontiguousarray(torch.stack((x, torch.zeros_like(x)), 1).numpy()), len(x), 1.0, out)
+    ref = torch.sigmoid(x.double()).numpy()
+    assert np.abs(out[:, 1] - ref).max() <= SAT_ATOL and (out[:, 1] >= 0).all()

@@ -272,6 +272,13 @@ __device__ __forceinline__ RowRegs<T> load_row(const T* row, int no, int lane) {
   return r;
 }
 
+// The objectness target of a matched cell is iou.detach().clamp(0) (utils/loss.py:155): torch's clamp PROPAGATES a NaN (fmaxf
+// would return 0), and torch.argsort (:156) ranks a NaN above every number.  A NaN box logit must reach lobj and the cell's
+// objectness gradient as it does in the reference, so that a GradScaler sees the same non-finite tensors.
+__device__ __forceinline__ float clamp0_nan(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ bool score_gt(float a, float b) { return (a != a) ? (b == b) : a > b; }
+__device__ __forceinline__ bool score_eq(float a, float b) { return a == b || (a != a && b != b); }
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_loss_entries_fwd(const LossDev* __restrict__ dp) {
   const LossDev& d = *dp;
@@ -311,7 +318,7 @@ __global__ __launch_bounds__(256) void k_loss_entries_fwd(const LossDev* __restr
         else {                                                  // :156-158 rows sorted by iou: the largest is written last
           const float4 tj = d.e_tbox[jj];
           const float cj = ciou_fwd_bwd(pb.x, pb.y, pb.w, pb.h, tj.x, tj.y, tj.z, tj.w).ciou;
-          if (cj > best || (cj == best && jj > w)) { best = cj; w = jj; }
+          if (score_gt(cj, best) || (score_eq(cj, best) && jj > w)) { best = cj; w = jj; }
         }
       }
       float iw = best;
@@ -319,7 +326,7 @@ __global__ __launch_bounds__(256) void k_loss_entries_fwd(const LossDev* __restr
         const float4 tj = d.e_tbox[w];
         iw = ciou_fwd_bwd(pb.x, pb.y, pb.w, pb.h, tj.x, tj.y, tj.z, tj.w).ciou;
       }
-      const float tobj = round_to_dtype<T>((1.0f - d.gr) + d.gr * round_to_dtype<T>(fmaxf(iw, 0.f)));   // :155,159
+      const float tobj = round_to_dtype<T>((1.0f - d.gr) + d.gr * round_to_dtype<T>(clamp0_nan(iw)));   // :155,159
       corr = bce_focal(x4, tobj, d.obj_pw, d.fl_gamma) - bce_focal(x4, 0.f, d.obj_pw, d.fl_gamma);
     }
     if (lane == 0) {
@@ -497,7 +504,7 @@ __global__ __launch_bounds__(256) void k_loss_entries_bwd(const LossDev* __restr
       const float4 tb = d.e_tbox[cur];
       const CiouOut co = ciou_fwd_bwd(pb.x, pb.y, pb.w, pb.h, tb.x, tb.y, tb.z, tb.w);
       if (!d.sort_obj_iou) { w = cur; iou_w = co.ciou; }
-      else if (co.ciou >= best) { best = co.ciou; w = cur; iou_w = co.ciou; }
+      else if (score_gt(co.ciou, best) || score_eq(co.ciou, best)) { best = co.ciou; w = cur; iou_w = co.ciou; }
       const float* tr = d.targets + (size_t)d.e_t[cur] * d.tcols;
       const int tc = (int)tr[1];
       const CslRow csl = csl_row(d, tr);
@@ -512,7 +519,7 @@ __global__ __launch_bounds__(256) void k_loss_entries_bwd(const LossDev* __restr
       }
     }
     (void)w;
-    const float tobj = round_to_dtype<T>((1.0f - d.gr) + d.gr * round_to_dtype<T>(fmaxf(iou_w, 0.f)));
+    const float tobj = round_to_dtype<T>((1.0f - d.gr) + d.gr * round_to_dtype<T>(clamp0_nan(iou_w)));
     const float g4 = bce_focal_grad(x4, tobj, d.obj_pw, d.fl_gamma) * s_obj;
     T* grow = (T*)d.grad[lv] + (size_t)cell * no;
 #pragma unroll
