@@ -514,6 +514,32 @@ size_t obb_process_batch_workspace_bytes(int64_t n, int64_t m);
 int obb_process_batch_f32(const float* det6, int64_t n, const float* lab5, int64_t m, const float* iouv, int niou, uint8_t* correct,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* process_batch with the ROTATED IoU -- the oriented-box mAP, which val.py can only reach offline through DOTA_devkit:
+ * val.py:69-90 with box_iou(labels, detections) replaced by single_box_iou_rotated<float>(label [cx cy l s theta], detection
+ * [cx cy l s theta]), the label FIRST: iou[l][d] is the value obb_rotated_iou_pairs_f32(a5 = label, b5 = detection) returns, bit
+ * for bit.  Both boxes are taken in the letterboxed frame as the rows carry them (the rotated IoU is invariant under scale_polys'
+ * uniform gain and shift: no pad, gain or clip is applied, and none of its rounding).  A pair is a candidate iff the classes are
+ * equal as floats and iou >= iouv[0] (NON-strict, unlike the NMS; a NaN IoU is never a candidate); a detection keeps its candidate
+ * of highest IoU, equal IoUs to the lower label row; a label keeps the lowest-indexed detection of its image that kept it;
+ * correct[d][k] = won && iou >= iouv[k].  The exact clip is skipped only for pairs PROVED to lie below iouv[0], which needs
+ * iouv[0] > 0; with iouv[0] <= 0 every pair of equal class is clipped.
+ *   obb_process_batch_obb_f32   one image: det7 (n,7) [cx cy l s theta conf cls], lab6 (m,6) [cls cx cy l s theta] -> correct
+ *                               (n, niou) bytes 0 / 1
+ *   obb_val_tail_batch_obb_f32  all images of a batch (bs <= 64) on the inputs of obb_val_tail_batch_rows_f32: det7 packed by
+ *                               det_off_host (det_row_host NULL) or at det_row_host[b]; targets (nt, tcols >= 7) -> stats
+ *                               (N, niou + 2) rows [correct as 0 / 1, conf, cls], packed by det_off_host
+ *   match_label [n] int32       the row of lab6 / targets the detection kept, or -1 -- set whether or not it won the label
+ *   match_iou   [n] float       that label's IoU, or -1.  Both arrays are REQUIRED: they are the state between the two launches
+ *                               (there is no workspace), and what an angle-error statistic needs.
+ * iouv: niou (1..16) device floats.  Stream-ordered, no synchronisation; the argument checks (bs outside 1..64, niou outside
+ * 1..16, tcols < 7, a NULL required pointer, inconsistent offsets) answer OBB_ERR_BAD_ARG before any device call and leave the
+ * outputs untouched.  n == 0: OBB_OK, no launch.  m == 0 / nt == 0: correct all 0, match_label -1, match_iou -1. */
+int obb_process_batch_obb_f32(const float* det7, int64_t n, const float* lab6, int64_t m, const float* iouv, int niou, uint8_t* correct,
+                              int32_t* match_label, float* match_iou, void* stream);
+int obb_val_tail_batch_obb_f32(const float* det7, const int64_t* det_row_host, const int64_t* det_off_host, int64_t bs, const float* targets,
+                               int64_t nt, int64_t tcols, const float* iouv, int niou, float* stats, int32_t* match_label, float* match_iou,
+                               void* stream);
+
 /* ConfusionMatrix.process_batch (utils/metrics.py:117-163) on the device, one launch per batch, one workgroup per image.
  * Per image: detections with conf > conf_thres (strict; NaN fails) against the labels; a pair is a candidate iff box_iou >
  * iou_thres (strict, float32; both thresholds are taken as float32, as torch compares a float32 tensor with a Python scalar).

@@ -18,6 +18,7 @@
 #include "dtype_device.h"
 #include "detect_math.h"
 #include "confusion_math.h"
+#include "geom.h"
 
 namespace obb {
 
@@ -657,8 +658,10 @@ __global__ void k_vt_dets(const float* __restrict__ det7, int n, ValTailImgs im,
 // `done` (optional, pinned host memory like `stats` may be): receives n once EVERY row has landed -- each workgroup makes its
 // rows visible system-wide (fence), then arrives on a device counter; the last one stores the flag.  The host polls it instead of
 // copying the rows back and waiting for the stream.
+// TOut = float: the rows above.  TOut = uint8_t (process_batch_obb's one-image form): correct[0 .. niou) alone, as bytes.
+template <typename TOut = float>
 __global__ void k_vt_stats(const float* __restrict__ det7, const int* __restrict__ best_label, const float* __restrict__ best_iou,
-                           ValTailImgs im, const float* __restrict__ iouv, int n, int niou, float* __restrict__ stats,
+                           ValTailImgs im, const float* __restrict__ iouv, int n, int niou, TOut* __restrict__ stats,
                            int* __restrict__ counter, long long* __restrict__ done) {
   const int d = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
@@ -683,11 +686,16 @@ __global__ void k_vt_stats(const float* __restrict__ det7, const int* __restrict
     }
     if (found && lane == l0) win = false;
   }
+  if constexpr (std::is_same<TOut, float>::value) {
   if (d < n) {
     float* o = stats + (size_t)d * (niou + 2);
     for (int k = 0; k < niou; k++) o[k] = (win && best_iou[d] >= iouv[k]) ? 1.f : 0.f;
     const float* row = det7 + ((size_t)row_b + (d - off_b)) * 7;
     o[niou] = row[5]; o[niou + 1] = row[6];
+  }
+  } else {
+    if (d < n)
+      for (int k = 0; k < niou; k++) stats[(size_t)d * niou + k] = (win && best_iou[d] >= iouv[k]) ? 1 : 0;
   }
   if (done != nullptr) {                                          // (kernel-uniform)
     __threadfence_system();
@@ -696,6 +704,149 @@ __global__ void k_vt_stats(const float* __restrict__ det7, const int* __restrict
       __hip_atomic_store(done, (long long)n, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
+
+// ---- process_batch with the ROTATED IoU (the oriented-box mAP): val.py:69-90 with box_iou replaced by
+// single_box_iou_rotated<float>(label [cx cy l s theta], detection [cx cy l s theta]) in the letterboxed frame of the rows -- the
+// value obb_rotated_iou_pairs_f32(a5 = label, b5 = detection) returns, bit for bit (riou_device.h).  Every other rule is
+// k_vt_dets': class equality as a float compare, iou >= iouv[0] non-strict (a NaN IoU is no candidate), a detection keeps its
+// candidate of highest IoU, ties to the lower label index; the label's winner and the rows are k_vt_stats' on the two arrays below.
+//   * one lane per detection; the labels of the one or two images a workgroup's detections belong to are staged in LDS as packed
+//     RotGeom records -- rbox_make_feat's double sin / cos once per label per workgroup -- with the class, the label's row and
+//     its image in the free slots of quad 3.  One tile when they fit kVtLabLds records (staged optimistically); else tiles over
+//     consecutive runs of kVtLabLds label rows, the queue drained before a tile is replaced.
+//   * a lane walks the tile (broadcast reads) and drops a pair of its image and class only on a PROOF that iou < iouv[0]:
+//     RotGeom::cheap_reject / rbox_certainly_disjoint prove "the reference returns exactly 0", the area-ratio bound and
+//     rbox_quick_bounds prove an upper bound -- all of them only while iouv[0] > 0 (`cull`); with iouv[0] <= 0 (or NaN) an IoU
+//     of 0 is itself a candidate and every pair of the class is clipped.
+//   * survivors go into the wave's LDS queue as (lane << 16 | tile slot); whenever it holds 64 entries, and at the end of a tile,
+//     one pair per lane runs the exact clip on the lane's scratch column -- the ~10^3-flop clip never runs for a handful of lanes.
+//     The detection's features come from their owner's registers (12 __shfl), the label's from the tile.
+//   * the result returns to its detection through a 64-bit LDS atomic max on (ordered IoU bits << 32 | ~label row): k_confusion's
+//     winner-slot idiom (cm::winner_key); the complement sends equal IoUs to the lower label row.
+// LDS: the tile 512 x 64 B = 32 KiB, clip scratch 2 waves x 12 KiB, 128 slots x 8 B, 2 queues x 128 x 4 B: 58.0 KiB + 4 B --
+// two workgroups in a CU's 160 KiB.  kBatch = false: one image, labels (m, 6) [cls cx cy l s theta] (im.bs = 1).
+constexpr int kVoThreads = 128, kVoWaves = kVoThreads / 64, kVoQueue = 128;
+// true only when the IoU the reference computes for (A, B) is PROVED to lie below thr (for thr > 0 only)
+__device__ __forceinline__ bool vo_proved_below(const RBoxFeat& A, const RBoxFeat& B, float thr) {
+  if (rbox_certainly_disjoint(A, B)) return true;                 // exactly 0
+  if (rbox_iou_upper_bound(A, B) < thr) return true;              // area ratio (+inf when it does not vouch)
+  IouBounds qb;
+  return rbox_quick_bounds(A, B, &qb) && qb.hi < thr;
+}
+template <bool kBatch>
+__global__ __launch_bounds__(kVoThreads) void k_vo_match(const float* __restrict__ det7, int n, ValTailImgs im,
+                                                         const float* __restrict__ labels, int nt, int lcols,
+                                                         const float* __restrict__ iouv, int* __restrict__ match_label,
+                                                         float* __restrict__ match_iou) {
+  __shared__ float4 s_lab[kVtLabLds * RotGeom::RECQ];
+  __shared__ float s_scr[kVoWaves][RotGeom::SCR * 64];
+  __shared__ unsigned long long s_best[kVoThreads];
+  __shared__ int s_q[kVoWaves][kVoQueue];
+  __shared__ int s_nl;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int d = blockIdx.x * kVoThreads + tid;
+  const bool valid = d < n;
+  const int d_first = blockIdx.x * kVoThreads, d_last = (d_first + kVoThreads < n ? d_first + kVoThreads : n) - 1;
+  int b_lo = 0;
+  while (b_lo + 1 < im.bs && d_first >= im.det_off[b_lo + 1]) b_lo++;
+  int b_hi = b_lo;
+  while (b_hi + 1 < im.bs && d_last >= im.det_off[b_hi + 1]) b_hi++;
+  // the lane's detection: features in registers (every lane stays to the end: the drain reads them with __shfl)
+  int b = b_lo;
+  RBoxFeat D = {};
+  float4 dq0 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float cls = 0.f;
+  if (valid) {
+    while (b + 1 < im.bs && d >= im.det_off[b + 1]) b++;
+    const float* row = det7 + ((size_t)im.det_row[b] + (d - im.det_off[b])) * 7;
+    D = rbox_make_feat(row[0], row[1], row[2], row[3], row[4]);
+    float4 q[RotGeom::RECQ];
+    RotGeom::pack(D, q);
+    dq0 = q[0];
+    cls = row[6];
+  }
+  const float thr0 = iouv[0];                                      // val.py:81  iou >= iouv[0]
+  const bool cull = thr0 > 0.f;
+  s_best[tid] = 0ull;                                              // (no key is 0)
+  int* q_w = s_q[wave];
+  float* scr = s_scr[wave] + lane;
+  int qn = 0;                                                      // entries in the wave's queue (wave-uniform)
+  // the exact IoU of the queue's last `cnt` (<= 64) entries, one per lane
+  auto drain = [&](int cnt) {
+    qn -= cnt;
+    __builtin_amdgcn_wave_barrier();
+    const bool has = lane < cnt;
+    const int ent = has ? q_w[qn + lane] : 0;
+    const int ql = ent >> 16, k = ent & 0xffff;
+    RBoxFeat B;
+    B.x = __shfl(D.x, ql); B.y = __shfl(D.y, ql); B.w = __shfl(D.w, ql); B.h = __shfl(D.h, ql);
+    B.sh = __shfl(D.sh, ql); B.cw = __shfl(D.cw, ql); B.ch = __shfl(D.ch, ql); B.sw = __shfl(D.sw, ql);
+    B.r = __shfl(D.r, ql); B.c = __shfl(D.c, ql); B.s = __shfl(D.s, ql); B.area = __shfl(D.area, ql);
+    if (has) {
+      const float4 l3 = s_lab[k * 4 + 3];
+      const RBoxFeat A = RotGeom::unpack(s_lab[k * 4], s_lab[k * 4 + 1], s_lab[k * 4 + 2], l3);
+      const float iou = rot_iou_value(A, B, scr);                  // (label, detection): the argument order is part of the value
+      if (iou >= thr0) atomicMax(&s_best[wave * 64 + ql], cm::winner_key(iou, ~__float_as_int(l3.z)));
+    }
+    __builtin_amdgcn_wave_barrier();
+  };
+  // rows [r0, r1) of the labels: the ones of the workgroup's images -> the tile, in arrival order (slots past the tile are dropped)
+  auto stage = [&](int r0, int r1) {
+    for (int l = r0 + tid; l < r1; l += kVoThreads) {
+      const float* t = labels + (size_t)l * lcols;
+      const int lb = kBatch ? (int)t[0] : 0;
+      if (lb < b_lo || lb > b_hi) continue;
+      const int k = atomicAdd(&s_nl, 1);
+      if (k >= kVtLabLds) continue;
+      const float* r = t + (kBatch ? 1 : 0);                       // [cls cx cy l s theta]
+      float4 q[RotGeom::RECQ];
+      RotGeom::pack(rbox_make_feat(r[1], r[2], r[3], r[4], r[5]), q);
+      q[3].y = r[0]; q[3].z = __int_as_float(l); q[3].w = __int_as_float(lb);
+      s_lab[k * 4] = q[0]; s_lab[k * 4 + 1] = q[1]; s_lab[k * 4 + 2] = q[2]; s_lab[k * 4 + 3] = q[3];
+    }
+  };
+  auto walk = [&](int tn) {
+    for (int k = 0; k < tn; k++) {
+      const float4 l0 = s_lab[k * 4], l3 = s_lab[k * 4 + 3];
+      bool push = valid && __float_as_int(l3.w) == b && l3.y == cls;
+      if (push && cull) {
+        if (RotGeom::cheap_reject(l0, dq0)) push = false;
+        else push = !vo_proved_below(RotGeom::unpack(l0, s_lab[k * 4 + 1], s_lab[k * 4 + 2], l3), D, thr0);
+      }
+      const unsigned long long mask = __ballot(push);
+      if (push) q_w[qn + __popcll(mask & ((1ull << lane) - 1ull))] = (lane << 16) | k;
+      qn += __popcll(mask);
+      if (qn >= 64) drain(64);                                     // (qn < 64 before the push: never more than 127 entries)
+    }
+    if (qn > 0) drain(qn);
+  };
+  if (tid == 0) s_nl = 0;
+  __syncthreads();
+  stage(0, nt);
+  __syncthreads();
+  const int nl = s_nl;
+  if (nl <= kVtLabLds) {
+    walk(nl);
+  } else {
+    for (int r0 = 0; r0 < nt; r0 += kVtLabLds) {                   // (a run of kVtLabLds rows cannot overflow the tile)
+      __syncthreads();
+      if (tid == 0) s_nl = 0;
+      __syncthreads();
+      stage(r0, r0 + kVtLabLds < nt ? r0 + kVtLabLds : nt);
+      __syncthreads();
+      walk(s_nl);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();                                 // (a slot is written by the lanes of its own wave only)
+  if (valid) {
+    const unsigned long long key = s_best[tid];
+    uint32_t u = (uint32_t)(key >> 32);
+    u ^= (u >> 31) ? 0x80000000u : 0xffffffffu;                    // cm::winner_key's bit map, inverted
+    match_label[d] = key ? (int)~(uint32_t)key : -1;
+    match_iou[d] = key ? __uint_as_float(u) : -1.f;
+  }
+}
+
 
 // ---- ConfusionMatrix.process_batch (utils/metrics.py:125-163) for every image of a batch in ONE launch: a workgroup is an
 // image, workgroups exchange nothing, and the only traffic between them is the final atomic adds into the matrix.  The rules
@@ -867,6 +1018,17 @@ __global__ __launch_bounds__(kCmThreads) void k_confusion(const float* __restric
   if (tid == 0 && s_oor) atomicAdd(&matrix[cells], (unsigned long long)s_oor);
 }
 
+// the two launches of the oriented tail: the match arrays, then k_vt_stats on them (TOut = float rows / uint8_t correct)
+template <bool kBatch, typename TOut>
+static int vo_launch(const float* det7, int64_t n, const ValTailImgs& im, const float* labels, int64_t nt, int64_t lcols,
+                     const float* iouv, int niou, TOut* out, int32_t* match_label, float* match_iou, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  k_vo_match<kBatch><<<(unsigned)((n + kVoThreads - 1) / kVoThreads), kVoThreads, 0, st>>>(
+      det7, (int)n, im, labels, (int)nt, (int)lcols, iouv, match_label, match_iou);
+  k_vt_stats<TOut><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(det7, match_label, match_iou, im, iouv, (int)n, niou, out, nullptr, nullptr);
+  return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
+}
+
 }  // namespace obb
 
 extern "C" {
@@ -898,7 +1060,7 @@ static int vt_fill_imgs(obb::ValTailImgs& im, const int64_t* det_row_host, const
     if (r < 0 || r > 0x7fffffff - (det_off_host[b + 1] - det_off_host[b])) return OBB_ERR_BAD_ARG;
     im.det_row[b] = (int)r;
   }
-  for (int b = 0; b < (int)bs; b++) {
+  for (int b = 0; img5_host && b < (int)bs; b++) {             // (NULL: the oriented tail, which works in the frame of the rows)
     const float* q = img5_host + (size_t)b * 5;                 // pad_x, pad_y, gain, native width, native height
     if (!(q[2] > 0.f)) return OBB_ERR_BAD_ARG;
     im.pad_x[b] = q[0]; im.pad_y[b] = q[1]; im.gain[b] = q[2]; im.shape_w[b] = q[3]; im.shape_h[b] = q[4];
@@ -924,7 +1086,7 @@ static int val_tail_batch_impl(const float* det7, const int64_t* det_row_host, c
   int* counter = (int*)(((uintptr_t)(best_iou + n) + 255) & ~(uintptr_t)255);              // (inside the 512 spare bytes)
   obb::k_vt_dets<<<(unsigned)((n + 127) / 128), 128, 0, st>>>(det7, (int)n, im, targets, (int)nt, (int)tcols, iouv, poly10, hbb6, polyn10, hbbn6,
                                                             best_label, best_iou, counter);
-  obb::k_vt_stats<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(det7, best_label, best_iou, im, iouv, (int)n, niou, stats, counter,
+  obb::k_vt_stats<float><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(det7, best_label, best_iou, im, iouv, (int)n, niou, stats, counter,
                                                               reinterpret_cast<long long*>(done));
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
@@ -968,6 +1130,29 @@ int obb_process_batch_f32(const float* det6, int64_t n, const float* lab5, int64
   obb::k_pb_best<<<(unsigned)((n + 127) / 128), 128, 0, st>>>(det6, (int)n, lab5, (int)m, iouv, best_label, best_iou, winner);
   obb::k_pb_correct<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(best_label, best_iou, winner, iouv, (int)n, niou, correct);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
+}
+
+int obb_process_batch_obb_f32(const float* det7, int64_t n, const float* lab6, int64_t m, const float* iouv, int niou, uint8_t* correct,
+                              int32_t* match_label, float* match_iou, void* stream) {
+  if (n < 0 || m < 0 || niou < 1 || niou > 16 || n > 0x7fffffff || m > 0x7fffffff) return OBB_ERR_BAD_ARG;
+  if (n == 0) return OBB_OK;
+  if (!det7 || !iouv || !correct || !match_label || !match_iou || (m > 0 && !lab6)) return OBB_ERR_BAD_ARG;
+  obb::ValTailImgs im = {};
+  im.bs = 1; im.det_off[1] = (int)n;
+  return obb::vo_launch<false, uint8_t>(det7, n, im, lab6, m, 6, iouv, niou, correct, match_label, match_iou, stream);
+}
+
+int obb_val_tail_batch_obb_f32(const float* det7, const int64_t* det_row_host, const int64_t* det_off_host, int64_t bs, const float* targets,
+                               int64_t nt, int64_t tcols, const float* iouv, int niou, float* stats, int32_t* match_label, float* match_iou,
+                               void* stream) {
+  if (bs < 1 || bs > obb::kValTailMaxBs || nt < 0 || nt > 0x7fffffff || niou < 1 || niou > 16 || !det_off_host || !iouv) return OBB_ERR_BAD_ARG;
+  if (nt > 0 && (!targets || tcols < 7)) return OBB_ERR_BAD_ARG;
+  obb::ValTailImgs im;
+  if (vt_fill_imgs(im, det_row_host, det_off_host, bs, nullptr) != OBB_OK) return OBB_ERR_BAD_ARG;
+  const int64_t n = det_off_host[bs];
+  if (n == 0) return OBB_OK;
+  if (!det7 || !stats || !match_label || !match_iou) return OBB_ERR_BAD_ARG;
+  return obb::vo_launch<true, float>(det7, n, im, targets, nt, tcols, iouv, niou, stats, match_label, match_iou, stream);
 }
 
 size_t obb_confusion_workspace_bytes(int64_t n_det, int64_t nt) {

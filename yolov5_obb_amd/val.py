@@ -60,6 +60,37 @@ def process_batch(detections, labels, iouv):
     return correct
 
 
+def process_batch_obb(pred, labels, iouv, return_match=False):
+    """process_batch (val.py:69-90) with the ROTATED IoU: the oriented-box `correct` matrix of one image.
+    Arguments:
+        pred (Array[N, 7]), cx, cy, l, s, theta, conf, class -- the rows non_max_suppression_obb returns
+        labels (Array[M, 6]), class, cx, cy, l, s, theta -- in the same (letterboxed) frame
+    Returns:
+        correct (Array[N, niou]) bool; with return_match also match_label (N) int32 -- the label row each detection kept,
+        -1 for none, whether or not it won that label -- and match_iou (N) float32, that label's IoU or -1.
+    iou[l, d] is ops.rotated_iou_pairs(label, detection) bit for bit; the rules are process_batch's (include/obb_hip.h)."""
+    _lib.require_cuda(pred, "pred")
+    if pred.dim() != 2 or pred.shape[1] != 7:
+        raise RuntimeError(f"process_batch_obb: pred must be (n,7), got {tuple(pred.shape)}")
+    if labels.dim() != 2 or labels.shape[1] != 6:
+        raise RuntimeError(f"process_batch_obb: labels must be (m,6), got {tuple(labels.shape)}")
+    dev = pred.device
+    det = _as_f32_cuda(pred, dev)
+    lab = _as_f32_cuda(labels, dev)
+    iv = _as_f32_cuda(iouv, dev)
+    n, m, niou = det.shape[0], lab.shape[0], iv.shape[0]
+    correct = torch.zeros((n, niou), dtype=torch.bool, device=dev)
+    match_label = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    match_iou = torch.full((n,), -1.0, dtype=torch.float32, device=dev)
+    if n:
+        with _lib.guard(dev):
+            rc = _lib.lib().obb_process_batch_obb_f32(_lib.ptr(det), n, _lib.ptr(lab) if m else 0, m, _lib.ptr(iv), niou,
+                                                      _lib.ptr(correct.view(torch.uint8)), _lib.ptr(match_label), _lib.ptr(match_iou),
+                                                      _lib.stream_ptr(dev))
+        _lib.check(rc, "obb_process_batch_obb_f32")
+    return (correct, match_label, match_iou) if return_match else correct
+
+
 _TAIL_MAX_BS = 64      # csrc/head.hip kValTailMaxBs: images per obb_val_tail_batch_f32 call
 _pin_cache = {}
 _arr_cache = {}
@@ -203,14 +234,80 @@ def val_tail_batch(preds, targets, shapes, iouv, want_boxes=False):
     return (out, (boxes, offs)) if want_boxes else out
 
 
+def _obb_tail_launch(L, packed, offs, bs, tg, nt, tcols, iv, niou, rows, row0, match_label, match_iou, dev, st):
+    """obb_val_tail_batch_obb_f32 on a batch laid out for the HBB tail (chunks of _TAIL_MAX_BS images): the stats rows go to
+    rows[row0 + d], the match arrays to [d], d = the packed row of the detection."""
+    import ctypes as C
+    null = C.c_void_p(0)
+    for b0 in range(0, bs, _TAIL_MAX_BS):
+        b1 = min(bs, b0 + _TAIL_MAX_BS)
+        k = b1 - b0
+        lo, hi = offs[b0], offs[b1]
+        if hi == lo:
+            continue
+        doff = (C.c_int64 * (k + 1))(*[o - lo for o in offs[b0:b1 + 1]])
+        tgk, ntk, base = tg, nt, None
+        if nt and (b0 or b1 < bs):                               # a chunk of a very large batch: its labels, re-based
+            base = torch.nonzero((tg[:, 0] >= b0) & (tg[:, 0] < b1))[:, 0]
+            tgk = tg[base].clone()
+            tgk[:, 0] -= b0
+            ntk = int(tgk.shape[0])
+        rc = L.obb_val_tail_batch_obb_f32(
+            C.c_void_p(packed.data_ptr() + lo * 28), null, C.cast(doff, C.c_void_p), k, C.c_void_p(tgk.data_ptr()) if ntk else null, ntk,
+            tcols, C.c_void_p(iv.data_ptr()), niou, C.c_void_p(rows.data_ptr() + (row0 + lo) * (niou + 2) * 4),
+            C.c_void_p(match_label.data_ptr() + lo * 4), C.c_void_p(match_iou.data_ptr() + lo * 4), C.c_void_p(st))
+        _lib.check(rc, "obb_val_tail_batch_obb_f32")
+        if base is not None and ntk:                             # rows of the chunk's label list -> rows of `targets`
+            ml = match_label[lo:hi]
+            ml.copy_(torch.where(ml >= 0, base.to(torch.int32)[ml.clamp(min=0).long()], ml))
+
+
+def val_tail_batch_obb(preds, targets, iouv, return_match=False):
+    """The oriented-box statistics of ALL images of a batch, what val.py:250 would append if process_batch compared rotated
+    boxes: per image (correct bool (n_i, niou), conf (n_i), cls (n_i)) on the HOST, like val_tail_batch.  Two launches.
+
+    preds    list of (n_i, 7) CUDA tensors [x y l s theta conf cls], the output of non_max_suppression_obb
+    targets  (nt, >= 7) labels of the batch [img cls cx cy l s theta ...] in pixels of the letterboxed frame
+    No shapes: both boxes stay in the letterboxed frame (the rotated IoU does not change under scale_polys).  With return_match
+    also, per image, (match_label int32: the row of `targets` each detection kept or -1, match_iou float32) on the device."""
+    bs = len(preds)
+    if bs == 0:
+        return ([], []) if return_match else []
+    dev = preds[0].device
+    if dev.type != "cuda":
+        _lib.require_cuda(preds[0], "pred")
+    counts = [p.shape[0] for p in preds]
+    offs = [0] * (bs + 1)
+    for b in range(bs):
+        offs[b + 1] = offs[b] + counts[b]
+    n = offs[bs]
+    niou = int(iouv.shape[0])
+    packed = _pack_dets(preds, dev, n)
+    tg = _as_f32_cuda(targets, dev) if targets.dim() == 2 and targets.shape[0] else None
+    nt, tcols = (tg.shape[0], tg.shape[1]) if tg is not None else (0, 0)
+    iv = _as_f32_cuda(iouv, dev)
+    rows = torch.empty((n, niou + 2), dtype=torch.float32, device=dev)
+    match_label = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    match_iou = torch.full((n,), -1.0, dtype=torch.float32, device=dev)
+    if n:
+        with _lib.guard(dev):
+            _obb_tail_launch(_lib.lib(), packed, offs, bs, tg, nt, tcols, iv, niou, rows, 0, match_label, match_iou, dev,
+                             _lib.stream_handle(dev))
+    arr = rows.cpu().numpy()
+    host = torch.from_numpy(arr)
+    out = list(zip(torch.from_numpy(arr[:, :niou] > 0.5).split(counts), host[:, niou].split(counts), host[:, niou + 1].split(counts)))
+    return (out, list(zip(match_label.split(counts), match_iou.split(counts)))) if return_match else out
+
+
 class ValStats:
     """The statistics of a whole validation run in DEVICE memory: what val.py:250 appends per image and :269 concatenates, as
     one (n, niou + 2) array of rows [correct x niou as 0 / 1, conf, cls] (the rows obb_val_tail_batch_f32 writes, in the order
     of the images) plus the class of every label -- the inputs of utils.metrics.ap_per_class, which then runs on them where
     they lie.  Nothing is copied to the host and nothing waits for the stream until ap_per_class() / cpu() is called."""
 
-    def __init__(self, niou=10, device=None, capacity=1 << 16):
+    def __init__(self, niou=10, device=None, capacity=1 << 16, obb=False):
         self.niou = int(niou)
+        self.obb = bool(obb)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("ValStats: device must be a CUDA/HIP device (no CPU path, by design)")
@@ -218,6 +315,10 @@ class ValStats:
         self._rows = torch.empty((max(1, int(capacity)), self.niou + 2), dtype=torch.float32, device=self.device)
         self._tcls = torch.empty(max(1, int(capacity) // 8), dtype=torch.float32, device=self.device)
         self._result = None
+        # obb=True: the same rows with process_batch on the ROTATED boxes (obb_val_tail_batch_obb_f32), row for row beside the others
+        self._rows_obb = torch.empty_like(self._rows) if self.obb else None
+        self._match = None
+        self._result_obb = None
 
     @property
     def rows(self):
@@ -271,6 +372,9 @@ class ValStats:
         packed = _pack_dets(preds, dev, n)
         iv = _as_f32_cuda(iouv, dev)
         self._rows = self._grown(self._rows, self.n, self.n + n)
+        if self.obb:
+            self._rows_obb = self._grown(self._rows_obb, self.n, self.n + n)
+            self._result_obb = None
         cols = self.niou + 2
         L = _lib.lib()
         null = C.c_void_p(0)
@@ -308,6 +412,10 @@ class ValStats:
                 if confusion is not None:
                     confusion._launch(L, part(packed, 7), C.cast(doff, C.c_void_p), k, hi - lo, C.c_void_p(tgk.data_ptr()) if ntk else null,
                                       ntk, tcols, C.cast(img5, C.c_void_p), dev, st)
+            if self.obb:                                         # (the match arrays of the last batch stay readable: last_match)
+                self._match = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
+                _obb_tail_launch(L, packed, offs, bs, tg, nt, tcols, iv, self.niou, self._rows_obb, self.n, self._match[0], self._match[1],
+                                 dev, st)
         self.n += n
         return (boxes, offs) if want_boxes else None
 
@@ -329,4 +437,41 @@ class ValStats:
     def cpu(self):
         """(correct bool (n, niou), conf (n), pcls (n), tcls (m)) numpy arrays: the four arrays of val.py:269."""
         arr = self.rows.cpu().numpy()
+        return arr[:, :self.niou] > 0.5, arr[:, self.niou].copy(), arr[:, self.niou + 1].copy(), self.target_cls.cpu().numpy()
+
+    # ---- obb=True: the oriented-box statistics, accessor for accessor
+    def _need_obb(self):
+        if not self.obb:
+            raise RuntimeError("ValStats: the oriented-box statistics need ValStats(obb=True)")
+
+    @property
+    def rows_obb(self):
+        """(n, niou + 2) float32 on the device: `rows` with `correct` from the rotated IoU (conf and cls are the same)."""
+        self._need_obb()
+        return self._rows_obb[:self.n]
+
+    @property
+    def last_match(self):
+        """(match_label int32, match_iou float32) of the last batch added, by packed detection row (None before any)."""
+        self._need_obb()
+        return self._match
+
+    def ap_per_class_obb(self):
+        """utils.metrics.ap_per_class over the oriented-box rows: the OBB mAP@0.5 and mAP@0.5:0.95 of everything added so far."""
+        return self._metrics_obb()[0]
+
+    def _metrics_obb(self):
+        self._need_obb()
+        if self._result_obb is None:
+            from .utils import metrics
+            self._result_obb = metrics.ap_from_rows(self.rows_obb, self.target_cls, self.niou)
+        return self._result_obb
+
+    @property
+    def any_tp_obb(self):
+        return self._metrics_obb()[1][1] > 0
+
+    def cpu_obb(self):
+        """cpu() of the oriented-box rows."""
+        arr = self.rows_obb.cpu().numpy()
         return arr[:, :self.niou] > 0.5, arr[:, self.niou].copy(), arr[:, self.niou + 1].copy(), self.target_cls.cpu().numpy()

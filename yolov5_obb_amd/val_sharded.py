@@ -41,7 +41,7 @@ def _sync(device):
 
 def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True, single_cls=False, augment=False, device=None,
         ap_per_class=None, names=None, nms=None, postprocess=None, match=None, niou=10, collect=True, device_metrics=False,
-        confusion_matrix=None):
+        confusion_matrix=None, obb_metrics=False):
     """The loop of val.py:180-250 over ``loader`` (this rank's shard, see shard_loader), then the gather.
 
     model(im) -> (out (b, A, no), train_out), like the reference's Model in eval mode.  ``loader`` yields
@@ -58,7 +58,10 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
     and "metrics" its 7-tuple, or None when nothing matched (val.py:270).
     confusion_matrix (with device_metrics=True): a utils.metrics.ConfusionMatrix that every batch is added to on the device
     (val.py:245-246 with plots=True); it comes back as "confusion_matrix".  One process only: its counters are plain sums that a
-    later change can all-reduce."""
+    later change can all-reduce.
+    obb_metrics=True (with device_metrics=True): every batch also goes through the oriented-box tail (val.ValStats(obb=True):
+    process_batch with the rotated IoU), and "metrics_obb" is the same 7-tuple over those rows -- the OBB mAP@0.5 and
+    mAP@0.5:0.95 beside the horizontal ones -- or None when nothing matched."""
     # the HIP path's tail runs once per BATCH (val.val_tail_batch: three launches, one copy); injected stand-ins keep the
     # reference's per-image loop
     batch_tail = None
@@ -84,7 +87,9 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
             raise RuntimeError("val_sharded.run: device_metrics=True needs a single process (world size 1)")
         if batch_tail is None or device.type != "cuda":
             raise RuntimeError("val_sharded.run: device_metrics=True needs a CUDA device and this package's own tail")
-        vstats = V.ValStats(niou=niou, device=device)
+        vstats = V.ValStats(niou=niou, device=device, obb=bool(obb_metrics))
+    elif obb_metrics:
+        raise RuntimeError("val_sharded.run: obb_metrics needs device_metrics=True")
     if confusion_matrix is not None:
         if world > 1:
             raise RuntimeError("val_sharded.run: confusion_matrix needs a single process (world size 1)")
@@ -167,6 +172,9 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
                "metrics": metrics if vstats.any_tp else None, "dt_batches": dt_batches, "val_stats": vstats}
         if confusion_matrix is not None:
             res["confusion_matrix"] = confusion_matrix
+        if obb_metrics:
+            metrics_obb = vstats.ap_per_class_obb()
+            res["metrics_obb"] = metrics_obb if vstats.any_tp_obb else None
         return res
     # ---- the one exchange: per-image tuples to rank 0, in the original order of the image list
     if gidx is None:
