@@ -188,6 +188,25 @@ int obb_eval_best_gt_f64(const double* dets8, const int32_t* det_img, int64_t nd
                          int64_t n_img, double* ovmax, int32_t* jmax, void* stream);
 
 /*
+ * DOTA Task-2 (horizontal box) evaluation: the same part of DOTA_devkit/dota_evaluation_task2.py's voc_eval (:177-202).
+ * Per detection, over the boxes of its own image, in IEEE double and in the reference's expression order:
+ *   iw = max(min(gx2, bx2) - max(gx1, bx1) + 1., 0.), ih alike, inters = iw * ih,
+ *   uni = (bx2 - bx1 + 1.) * (by2 - by1 + 1.) + (gx2 - gx1 + 1.) * (gy2 - gy1 + 1.) - inters, overlaps = inters / uni
+ * with numpy's maximum / minimum (a NaN operand is the result) and no `overlaps > 0` gate, then np.max / np.argmax.
+ *   dets4   (nd) rows of det_stride >= 4 doubles, the first four xmin ymin xmax ymax (BB[d, :] of a wider row works)
+ *   det_img (nd) int32     image index of a detection; one outside [0, n_img) is treated as an image without boxes
+ *   gts4    (ng, 4) doubles, already truncated by the caller (:34-37), image i at gt_off[i] .. gt_off[i+1]
+ *   ovmax   (nd) doubles   the first maximum in list order; NaN: some overlap was NaN; -inf: the image has no box.
+ *                          A NaN is written as the canonical quiet NaN: payload and sign are not the reference's (numpy's
+ *                          0 / 0 on x86 has the sign bit set); every other value has the reference's bits
+ *   jmax    (nd) int32     its index within the image's list (the first NaN with NaN; -1 with -inf)
+ * No workspace.  Stream-ordered, no synchronisation.  det_stride < 4, a negative count or a NULL required pointer with
+ * nd > 0: OBB_ERR_BAD_ARG before any device call; nd == 0: OBB_OK, nothing is launched.
+ */
+int obb_eval_best_gt_hbb_f64(const double* dets4, int64_t det_stride, const int32_t* det_img, int64_t nd, const double* gts4,
+                             const int32_t* gt_off, int64_t n_img, double* ovmax, int32_t* jmax, void* stream);
+
+/*
  * Host-side text I/O of the merge (no device work; csrc/textio.hip).  obb_task1_parse_tiles restates
  * DOTA_devkit/ResultMerge_multi_process.py:186-213 for a whole Task1_<class>.txt buffer: per line
  * `<orig>__<rate>__<x>___<y> score x1 y1 .. x4 y4` -> dets9[line] = [8 source-image coordinates (poly + x|y) / rate,

@@ -126,11 +126,17 @@ def read_detections(detfile):
     got = _read_detections_native(detfile)
     if got is not None:
         return got
+    return read_detections_text(detfile, lambda ncols: ncols == 10)
+
+
+def read_detections_text(detfile, width_ok):
+    """`image score v ..` per line without the native reader: pandas' C reader with the round-trip float parser when every line
+    has the same number of columns and width_ok(that number) holds, line by line -- the reference's statements -- otherwise."""
     try:
         import pandas as pd
         df = pd.read_csv(detfile, sep=' ', header=None, float_precision='round_trip', dtype={0: str}, skip_blank_lines=False)
-        if df.shape[1] == 10 and not df.isna().any().any():
-            return df[0].tolist(), df[1].to_numpy(dtype=np.float64), df[[2, 3, 4, 5, 6, 7, 8, 9]].to_numpy(dtype=np.float64)
+        if width_ok(df.shape[1]) and not df.isna().any().any():
+            return df[0].tolist(), df[1].to_numpy(dtype=np.float64), df[list(range(2, df.shape[1]))].to_numpy(dtype=np.float64)
     except Exception:
         pass
     with open(detfile, 'r') as f:
@@ -183,9 +189,14 @@ def voc_eval(detpath, annopath, imagesetfile, classname, ovthresh=0.5, use_07_me
     sorted_ind = np.argsort(-confidence)                 # :163
     BB = BB[sorted_ind, :]
     det_img = np.array([index[image_ids[x]] for x in sorted_ind], dtype=np.int32)   # KeyError for an unlisted image, as :169
-    nd = len(det_img)
 
     ovmax, jmax = best_gt(BB, det_img, np.array(gts, dtype=np.float64).reshape(-1, 8), gt_off)
+    return pr_curve(ovmax, jmax, det_img, gt_off, difficult, npos, ovthresh, use_07_metric)
+
+
+def pr_curve(ovmax, jmax, det_img, gt_off, difficult, npos, ovthresh, use_07_metric):
+    """:225-249 from the per-detection (ovmax, jmax) in confidence order: TP / FP marks, rec, prec, ap."""
+    nd = len(det_img)
     tp = np.zeros(nd)
     fp = np.zeros(nd)
     hit = ovmax > ovthresh                               # NaN and -inf: False (:225)

@@ -247,6 +247,103 @@ __global__ __launch_bounds__(64 * kEvalWaves) void k_eval_best_gt(const double* 
   }
 }
 
+// DOTA Task-2 evaluation, the det x GT part of voc_eval (DOTA_devkit/dota_evaluation_task2.py:177-202): horizontal boxes,
+// the +1 convention, no `overlaps > 0` gate, np.max / np.argmax over the boxes of the detection's image.
+// numpy's maximum / minimum of doubles: a NaN operand is the result (fmax / fmin would drop it).
+__device__ __forceinline__ double np_max(double a, double b) { return (a >= b || a != a) ? a : b; }
+__device__ __forceinline__ double np_min(double a, double b) { return (a <= b || a != a) ? a : b; }
+
+struct Box4 { double x1, y1, x2, y2; };
+
+// a row of four doubles as two double2 when the row is 16-byte aligned (wave-uniform flag), as four doubles otherwise
+__device__ __forceinline__ Box4 load_box4(const double* p, bool aligned) {
+  Box4 b;
+  if (aligned) {
+    const double2 lo = reinterpret_cast<const double2*>(p)[0], hi = reinterpret_cast<const double2*>(p)[1];
+    b.x1 = lo.x; b.y1 = lo.y; b.x2 = hi.x; b.y2 = hi.y;
+  } else {
+    b.x1 = p[0]; b.y1 = p[1]; b.x2 = p[2]; b.y2 = p[3];
+  }
+  return b;
+}
+
+// :186-199 in the reference's expression order (barea = (bx2 - bx1 + 1.) * (by2 - by1 + 1.), a Python scalar there)
+__device__ __forceinline__ double hbb_overlap_task2(const Box4& g, const Box4& b, double barea) {
+  const double iw = np_max(np_min(g.x2, b.x2) - np_max(g.x1, b.x1) + 1., 0.);
+  const double ih = np_max(np_min(g.y2, b.y2) - np_max(g.y1, b.y1) + 1., 0.);
+  const double inters = iw * ih;
+  const double uni = barea + (g.x2 - g.x1 + 1.) * (g.y2 - g.y1 + 1.) - inters;
+  return inters / uni;
+}
+
+// running np.max / np.argmax of one lane over ascending j: the first maximum, the first NaN
+// (selects, not branches on references: the compiler otherwise keeps the two indices in scratch memory)
+__device__ __forceinline__ void best_take(double v, int j, double& best, int& bestj, int& nanj) {
+  const bool isn = v != v;
+  const bool up = !isn && (bestj < 0 || v > best);
+  nanj = (isn && j < nanj) ? j : nanj;
+  best = up ? v : best;
+  bestj = up ? j : bestj;
+}
+
+// One-wave workgroups, one LANE per detection (grid-stride over groups of 64 detections).  A lane whose image has at most
+// kHbbSerialMax boxes walks the list alone; the detections with longer lists are then taken one at a time by the whole wave
+// (their box broadcast from the owning lane, lanes over the list, the wave reduction of k_eval_best_gt).  No LDS.
+constexpr int kHbbSerialMax = 64;
+constexpr int kHbbMaxGrid = 4096;
+__global__ __launch_bounds__(64) void k_eval_best_gt_hbb(const double* __restrict__ dets4, long long det_stride, int dets_aligned,
+                                                        const int32_t* __restrict__ det_img, long long nd,
+                                                        const double* __restrict__ gts4, int gts_aligned,
+                                                        const int32_t* __restrict__ gt_off, long long n_img,
+                                                        double* __restrict__ ovmax, int32_t* __restrict__ jmax) {
+  const int lane = threadIdx.x;
+  for (long long d0 = (long long)blockIdx.x * 64; d0 < nd; d0 += (long long)gridDim.x * 64) {
+    const long long d = d0 + lane;
+    const bool valid = d < nd;
+    Box4 B = {0.0, 0.0, 0.0, 0.0};
+    int g0 = 0, g1 = 0;
+    if (valid) {
+      B = load_box4(dets4 + d * det_stride, dets_aligned != 0);
+      const long long img = det_img[d];
+      if (img >= 0 && img < n_img) { g0 = gt_off[img]; g1 = gt_off[img + 1]; }
+    }
+    const double barea = (B.x2 - B.x1 + 1.) * (B.y2 - B.y1 + 1.);
+    const int len = g1 - g0;
+    double best = -INFINITY;
+    int bestj = -1, nanj = 0x7fffffff;
+    if (len <= kHbbSerialMax) {
+      for (int j = 0; j < len; j++)
+        best_take(hbb_overlap_task2(load_box4(gts4 + (long long)(g0 + j) * 4, gts_aligned != 0), B, barea), j, best, bestj, nanj);
+    }
+    unsigned long long todo = __ballot(len > kHbbSerialMax);
+    while (todo) {
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      Box4 S;
+      S.x1 = __shfl(B.x1, src); S.y1 = __shfl(B.y1, src); S.x2 = __shfl(B.x2, src); S.y2 = __shfl(B.y2, src);
+      const double sarea = __shfl(barea, src);
+      const int s0 = __shfl(g0, src), slen = __shfl(len, src);
+      double sb = -INFINITY;
+      int sj = -1, sn = 0x7fffffff;
+      for (int j = lane; j < slen; j += 64)
+        best_take(hbb_overlap_task2(load_box4(gts4 + (long long)(s0 + j) * 4, gts_aligned != 0), S, sarea), j, sb, sj, sn);
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        const double ob = __shfl_xor(sb, off);
+        const int oj = __shfl_xor(sj, off), on = __shfl_xor(sn, off);
+        if (oj >= 0 && (sj < 0 || ob > sb || (ob == sb && oj < sj))) { sb = ob; sj = oj; }
+        if (on < sn) sn = on;
+      }
+      if (lane == src) { best = sb; bestj = sj; nanj = sn; }
+    }
+    if (valid) {
+      const bool isn = nanj != 0x7fffffff;
+      ovmax[d] = isn ? (double)NAN : best;
+      jmax[d] = isn ? nanj : bestj;
+    }
+  }
+}
+
 }  // namespace obb
 
 using namespace obb;
@@ -292,6 +389,18 @@ int obb_eval_best_gt_f64(const double* dets8, const int32_t* det_img, int64_t nd
   int64_t nb = (nd + kEvalWaves - 1) / kEvalWaves;
   if (nb > 256 * 16) nb = 256 * 16;
   k_eval_best_gt<<<(unsigned)nb, 64 * kEvalWaves, 0, (hipStream_t)stream>>>(dets8, det_img, nd, gts8, gt_off, ovmax, jmax);
+  return OBB_CHECK_LAUNCH();
+}
+
+int obb_eval_best_gt_hbb_f64(const double* dets4, int64_t det_stride, const int32_t* det_img, int64_t nd, const double* gts4,
+                             const int32_t* gt_off, int64_t n_img, double* ovmax, int32_t* jmax, void* stream) {
+  if (det_stride < 4 || nd < 0 || n_img < 0 || (nd > 0 && (!dets4 || !det_img || !gt_off || !ovmax || !jmax))) return OBB_ERR_BAD_ARG;
+  if (nd == 0) return OBB_OK;
+  int64_t nb = (nd + 63) / 64;
+  if (nb > kHbbMaxGrid) nb = kHbbMaxGrid;
+  const int dets_aligned = (det_stride & 1) == 0 && ((uintptr_t)dets4 & 15) == 0, gts_aligned = ((uintptr_t)gts4 & 15) == 0;
+  k_eval_best_gt_hbb<<<(unsigned)nb, 64, 0, (hipStream_t)stream>>>(dets4, det_stride, dets_aligned, det_img, nd, gts4, gts_aligned,
+                                                                  gt_off, n_img, ovmax, jmax);
   return OBB_CHECK_LAUNCH();
 }
 
