@@ -251,11 +251,11 @@ int64_t obb_task1_format_rows(const char* text_host, const int32_t* name_off_hos
  *               by a kernel that also builds the NMS records (six launches fewer); larger -> the multi-workgroup sorts of
  *               csrc/segsort.h / csrc/psrs_sort.h.  The in-LDS sort takes at most OBB_NMS_SORT_LDS_MAX candidates of an image:
  *               with a hint in 1 .. OBB_NMS_SORT_LDS_HINT and status[1] (low word) > OBB_NMS_SORT_LDS_MAX after the call, such
- *               images were left EMPTY -- call again with that count as the hint (the Python layer does).
+ *               images were left EMPTY -- call again with that count as the hint.
  *               bits 32..60 the largest NMS segment (boxes of one class of one image).  1 .. OBB_NMS_SMALL_SEG together with the
  *               in-LDS sort and iou_thres >= 0 selects the one-workgroup-per-segment NMS kernel (csrc/nms_small.h); a call that
  *               meets a larger segment there sets status[0] = -1: NOTHING of its output is valid, call again with the
- *               segment size status[1] reports (the Python layer does).  0 or larger: the persistent kernel.
+ *               segment size status[1] reports.  0 or larger: the persistent kernel.
  *               With out_packed = 0 that kernel's (image, class) workgroups also ORDER their class themselves (round 6: no sort
  *               launch; OBB_NMS_SELF_SORT above) and the reported size is the largest class of any image of up to
  *               OBB_NMS_SORT_LDS_MAX candidates; behind the sort kernel an image above OBB_NMS_SORT_LDS_MAX / 2 candidates is
@@ -268,7 +268,9 @@ int64_t obb_task1_format_rows(const char* text_host, const int32_t* name_off_hos
  *               combinations: microseconds for the stray sub-pixel box of a trained detector) and keeps the class segments of every
  *               image that passes; without it -- and for an image that fails, is above those bounds, or holds a box whose circle
  *               leaves a 0.95 max_wh window -- the image runs as the reference's single list.  Either way the rows are the reference's.
- *               Apart from the two retry cases the result does not depend on the hint.
+ *               Apart from the two retry cases the result does not depend on the hint.  The caller's side of all this -- which word to
+ *               hand in, which of the retry cases a call ended in, what to keep for the next call of the shape -- is implemented once,
+ *               as host code of this library: obb_nms_obb_hints_* below.
  *   out         [bs][max_det][7] fp32 rows [x y l s theta conf cls];  out_count [bs] int64 (-1: device-side abort);
  *               out_packed != 0: the rows of image b start right behind those of image b-1 (row sum(out_count[0..b-1]))
  *               instead of at row b*max_det -- the same buffer size is required, one split instead of bs slices on the host.
@@ -357,6 +359,49 @@ int obb_non_max_suppression_obb_head(int nl, const void* const* conv_out, int dt
                                      int64_t n_extra, int64_t cap_img, int64_t expected_cand, float* out, int out_packed,
                                      int64_t* out_count, int64_t* status, void* ws, size_t ws_bytes, void* state, size_t state_bytes,
                                      void* stream);
+
+/* The caller's side of the four fused entries above, as host code (csrc/nmsobb_hints.h: no device call, no allocation, no state
+ * but the struct): the reference implementation of what to do around a call, used by both bindings of this repository.  A caller
+ * keeps one obb_nms_obb_hints per input shape (and per thread, device and conf_thres: other batches say nothing about this one's).
+ *
+ *   obb_nms_obb_hints h;  obb_nms_obb_hints_init(&h);                 once per shape
+ *   int64_t cap_img = obb_nms_obb_hints_cap(&h, worst);               per call; worst = A * (multi_label ? nc : 1) + n_extra
+ *   for (;;) {
+ *     entry(..., cap_img, obb_nms_obb_hints_word(&h), ..., out_count, status, ws sized for cap_img, ...);
+ *     ... wait until out_count[0..bs) and status[0..1] are on the host ...
+ *     int action = obb_nms_obb_hints_update(&h, &cap_img, worst, out_count, bs, status);
+ *     if (action == OBB_HINTS_DONE) break;                            out / out_count are valid; h holds the next call's hints
+ *     if (action == OBB_HINTS_RETRY_SMALL_GRID) obb_nms_set_max_grid(8) -- or give up if that was done already
+ *   }                                                                 (restore obb_nms_set_max_grid(0) behind the loop)
+ *
+ * obb_nms_obb_hints_update reads status[1] (bit 62 -> small_boxes, bit 61 -> small_resolved) and then decides, in this order:
+ *   status[0] == -1              a segment above OBB_NMS_SMALL_SEG met the small-segment kernel: nothing is valid.  seg = the
+ *                                reported segment (at least OBB_NMS_SMALL_SEG + 1), held; OBB_HINTS_RETRY
+ *   some out_count[b] < 0        a barrier of the persistent kernel timed out: OBB_HINTS_RETRY_SMALL_GRID, h unchanged otherwise
+ *   status[0] > *cap_img         *cap_img = min(worst, max(status[0], 2 * *cap_img)); OBB_HINTS_RETRY (size the workspace again)
+ *   a hint in 1 .. OBB_NMS_SORT_LDS_HINT and more than OBB_NMS_SORT_LDS_MAX candidates in an image
+ *                                such images were left empty: cand = the reported count, held; OBB_HINTS_RETRY
+ *   otherwise                    OBB_HINTS_DONE: cap = *cap_img, cand and seg = what status[1] reports.  A regime that a retry
+ *                                of this or an earlier call selected is held for 8 calls -- cand stays above OBB_NMS_SORT_LDS_HINT,
+ *                                seg above OBB_NMS_SMALL_SEG -- unless the batch falls 25 % below that limit (a reported segment
+ *                                of 0, "not known on this path", does not release it): a stream whose batches hover around a
+ *                                limit does not pay the repeat on every other batch.
+ * Forcing a hint (cand = 0: the generic sort; seg = 1: the small-segment kernel) is a plain store to the field, with its hold = 0. */
+typedef struct obb_nms_obb_hints {
+  int64_t cap;                         /* candidate slots per image that sufficed last time (0: none yet)                  */
+  int64_t cand, seg;                   /* expected_cand bits 0..31 and 32..60 of the next call                             */
+  int64_t hold_cand, hold_seg;         /* calls the larger regime is still held                                            */
+  int64_t small_boxes, small_resolved; /* status[1] bits 62 and 61 of the previous call (0 / 1); the first is handed back  */
+  int64_t reserved;
+} obb_nms_obb_hints;
+#define OBB_HINTS_DONE 0
+#define OBB_HINTS_RETRY 1
+#define OBB_HINTS_RETRY_SMALL_GRID 2
+void obb_nms_obb_hints_init(obb_nms_obb_hints* hints_host);
+int64_t obb_nms_obb_hints_cap(const obb_nms_obb_hints* hints_host, int64_t worst);
+int64_t obb_nms_obb_hints_word(const obb_nms_obb_hints* hints_host);
+int obb_nms_obb_hints_update(obb_nms_obb_hints* hints_host, int64_t* cap_img_host, int64_t worst, const int64_t* out_count_host,
+                             int64_t bs, const int64_t* status_host);
 
 /* ------------------------------------------------------------------ training loss -------------------- */
 

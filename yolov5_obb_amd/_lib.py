@@ -55,6 +55,10 @@ SIGNATURES = {
                                               _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "obb_non_max_suppression_obb_head": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _i32, _i32, _i32,
                                                 _i64, _i64, _f32, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "obb_nms_obb_hints_init": (None, [_vp]),                        # hints: NmsObbHints (below), host memory
+    "obb_nms_obb_hints_cap": (_i64, [_vp, _i64]),
+    "obb_nms_obb_hints_word": (_i64, [_vp]),
+    "obb_nms_obb_hints_update": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp]),
     "obb_loss_workspace_bytes": (_sz, [_vp, _i64]),
     "obb_loss_build_targets": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
     "obb_loss_export_targets": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -98,6 +102,11 @@ class TtaPass(C.Structure):
                 ("conv_out", _vp * DETECT_MAX_LEVELS), ("ny", _i64 * DETECT_MAX_LEVELS),
                 ("nx", _i64 * DETECT_MAX_LEVELS), ("stride", _f32 * DETECT_MAX_LEVELS),
                 ("anchors_px", _f32 * 2 * MAX_ANCHORS * DETECT_MAX_LEVELS)]
+
+
+class NmsObbHints(C.Structure):
+    """obb_nms_obb_hints of include/obb_hip.h (what a caller of the fused NMS entries keeps per input shape)."""
+    _fields_ = [(name, _i64) for name in ("cap", "cand", "seg", "hold_cand", "hold_seg", "small_boxes", "small_resolved", "reserved")]
 
 
 def lib():

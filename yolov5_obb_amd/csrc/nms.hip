@@ -1013,6 +1013,7 @@ static int run_nms_rot64(const double* dets5, const double* scores, int64_t n, f
 
 #include "nmsobb_impl.h"
 #include "nms_head.h"
+#include "nmsobb_hints.h"
 
 using namespace obb;
 

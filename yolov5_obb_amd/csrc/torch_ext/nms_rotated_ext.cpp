@@ -37,6 +37,7 @@ namespace {
 #define OBB_API(X)                                                                                                         \
   X(obb_version) X(obb_nms_set_max_grid) X(obb_nms_workspace_bytes) X(obb_nms_rotated_f32) X(obb_nms_rotated_f64)       \
   X(obb_nms_poly_f32) X(obb_nms_obb_workspace_bytes) X(obb_nms_obb_state_bytes) X(obb_non_max_suppression_obb_st) X(obb_non_max_suppression_obb_head)                                   \
+  X(obb_nms_obb_hints_init) X(obb_nms_obb_hints_cap) X(obb_nms_obb_hints_word) X(obb_nms_obb_hints_update)                \
   X(obb_val_tail_batch_workspace_bytes) X(obb_val_tail_batch_rows_f32)
 
 struct Api {
@@ -219,51 +220,47 @@ at::Tensor nms_poly(const at::Tensor& dets, double iou_threshold) {
 
 // ---------------------------------------------------------------- non_max_suppression_obb (utils/general.py:772-862)
 constexpr int64_t kMaxWh = 4096, kMaxNms = 30000, kCsl = 180;          // utils/general.py:793-794, 784
-constexpr int64_t kHold = 8;                                           // calls a regime is held after a repeated call (hysteresis)
 
-struct ShapeKey {
-  int dev; int64_t A, nc; bool multi; uint32_t conf_bits;
-  bool operator<(const ShapeKey& o) const {
-    return std::tie(dev, A, nc, multi, conf_bits) < std::tie(o.dev, o.A, o.nc, o.multi, o.conf_bits);
-  }
-};
-struct ShapeMemo {
-  int64_t cap = 0;                             // candidate slots per image that sufficed last time
-  int64_t cand = OBB_NMS_SORT_LDS_HINT;        // largest candidate count of an image in the previous call: the sort hint.  No history:
-                                               // the regime of the reference's default thresholds (a few thousand candidates per image)
-  int64_t seg = 1;                             // largest NMS segment of the previous call: chooses the NMS kernel (no history: small)
-  bool small_resolved = false;                 // ... and (informational) such an image kept its class segments in that call
-  bool small_boxes = false;                    // the previous call met boxes with a sub-pixel side: the next one runs the cross-class check
-  int hold_seg = 0, hold_cand = 0;             // > 0: a call was repeated because its hint undersold it -- keep the larger regime this
-                                               // many calls unless the batch falls clearly (25 %) below the limit: a stream whose
-                                               // batches hover around a limit does not pay the repeat on every other batch
-};
-
-std::map<ShapeKey, ShapeMemo>& shape_memos() {            // per calling thread: other threads' batches say nothing about this one's
-  static thread_local std::map<ShapeKey, ShapeMemo> memos;
-  return memos;
+// The hints of a shape (include/obb_hip.h: obb_nms_obb_hints), per calling thread: other threads' batches say nothing about this one's
+using ShapeKey = std::tuple<int, int64_t, int64_t, bool, uint32_t>;     // device, A, nc, multi_label, conf_thres as float bits
+constexpr size_t kMaxShapes = 512;                   // thread churn or a swept threshold must not grow the map without bound; hints only:
+                                                     // forgetting them costs the next call of every shape one repeated call at most
+std::map<ShapeKey, obb_nms_obb_hints>& shape_hints() {
+  static thread_local std::map<ShapeKey, obb_nms_obb_hints> hints;
+  return hints;
 }
-uint32_t conf_key(double conf_thres) {
+ShapeKey shape_key(int dev, int64_t A, int64_t nc, bool multi, double conf_thres) {
   const float f = (float)conf_thres;
   uint32_t b;
   std::memcpy(&b, &f, 4);
-  return b;
+  return ShapeKey{dev, A, nc, multi, b};
 }
-// Introspection of the hint memo (tests, tools): the state of a shape, forcing a hint, forgetting everything.
-void hints_clear() { shape_memos().clear(); }
+obb_nms_obb_hints& hints_of(const ShapeKey& key) {
+  auto& m = shape_hints();
+  auto it = m.find(key);
+  if (it != m.end()) return it->second;
+  if (m.size() >= kMaxShapes) m.clear();
+  obb_nms_obb_hints& h = m[key];
+  api.obb_nms_obb_hints_init(&h);
+  return h;
+}
+// Introspection of the hints (tests, tools): the state of a shape, forcing a hint, forgetting the calling thread's shapes.
+void hints_clear() { shape_hints().clear(); }
 py::object hint_get(int dev, int64_t A, int64_t nc, bool multi, double conf_thres) {
-  auto& m = shape_memos();
-  auto it = m.find(ShapeKey{dev, A, nc, multi, conf_key(conf_thres)});
+  auto& m = shape_hints();
+  auto it = m.find(shape_key(dev, A, nc, multi, conf_thres));
   if (it == m.end()) return py::none();
+  const obb_nms_obb_hints& h = it->second;
   py::dict d;
-  d["cap"] = it->second.cap; d["cand"] = it->second.cand; d["seg"] = it->second.seg;
-  d["hold_cand"] = it->second.hold_cand; d["hold_seg"] = it->second.hold_seg; d["small_boxes"] = it->second.small_boxes; d["small_resolved"] = it->second.small_resolved;
+  d["cap"] = h.cap; d["cand"] = h.cand; d["seg"] = h.seg; d["hold_cand"] = h.hold_cand; d["hold_seg"] = h.hold_seg;
+  d["small_boxes"] = h.small_boxes != 0; d["small_resolved"] = h.small_resolved != 0;
   return std::move(d);
 }
 void hint_set(int dev, int64_t A, int64_t nc, bool multi, double conf_thres, int64_t cand, int64_t seg) {
-  ShapeMemo& e = shape_memos()[ShapeKey{dev, A, nc, multi, conf_key(conf_thres)}];
-  if (cand >= 0) { e.cand = cand; e.hold_cand = 0; }
-  if (seg >= 0) { e.seg = seg; e.hold_seg = 0; }
+  need_api();
+  obb_nms_obb_hints& h = hints_of(shape_key(dev, A, nc, multi, conf_thres));
+  if (cand >= 0) { h.cand = cand; h.hold_cand = 0; }
+  if (seg >= 0) { h.seg = seg; h.hold_seg = 0; }
 }
 
 // classes= and the label rows (utils/general.py:807-813, prepared by the Python layer as [img, x, y, l, s, theta, conf, cls]) as the
@@ -289,16 +286,16 @@ struct NmsOpts {
 };
 
 // The call loop of both fused entries (obb_non_max_suppression_obb_st, obb_non_max_suppression_obb_head): workspace, caller-kept
-// state, polled counters, the retry cases of include/obb_hip.h and the hint memo of the shape.  launch(cap_img, expected_cand, out,
-// out_count, status, ws, ws_bytes, state, state_bytes, stream) makes one call of the entry with out_packed = 0.
+// state, polled counters, and the shape's hints and retries as the library decides them (obb_nms_obb_hints_*).  launch(cap_img,
+// expected_cand, out, out_count, status, ws, ws_bytes, state, state_bytes, stream) makes one call of the entry with out_packed = 0.
 template <class Launch>
 std::vector<at::Tensor> run_fused(const at::Device dev, int64_t bs, int64_t A, int64_t nc, bool multi, double conf_thres, bool agnostic,
                                   int64_t max_det, int64_t n_extra, Launch&& launch) {
   std::vector<at::Tensor> result;
   static thread_local std::map<std::tuple<int64_t, int64_t, int64_t, int, bool>, size_t> ws_memo;
-  ShapeMemo& memo = shape_memos()[ShapeKey{(int)dev.index(), A, nc, multi, conf_key(conf_thres)}];
+  obb_nms_obb_hints& hints = hints_of(shape_key((int)dev.index(), A, nc, multi, conf_thres));
   const int64_t worst = A * (multi ? nc : 1) + n_extra;
-  int64_t cap = std::min(worst, std::max<int64_t>(memo.cap, 65536));
+  int64_t cap = api.obb_nms_obb_hints_cap(&hints, worst);
 
   c10::DeviceGuard guard(dev);
   const auto stream = c10::hip::getCurrentHIPStream(dev.index());
@@ -306,9 +303,7 @@ std::vector<at::Tensor> run_fused(const at::Device dev, int64_t bs, int64_t A, i
                                                                                                        // the NMS kernel writes them itself, one launch less)
   Pinned& meta = pinned_words(dev.index(), 1, bs + 2);                                                 // counts[bs] + status[2]
   AbortRetry retry;
-  int64_t seg_max = 0, cand_max = 0;
-  for (;;) {
-    const int64_t hint = memo.cand & 0xffffffffll, seg_hint = memo.seg & 0x1fffffffll;
+  for (bool done = false; !done;) {
     const auto wkey = std::make_tuple(bs, cap, nc, (int)agnostic, retry.capped);
     auto it = ws_memo.find(wkey);
     if (it == ws_memo.end()) it = ws_memo.emplace(wkey, api.obb_nms_obb_workspace_bytes(bs, cap, nc, agnostic ? 1 : 0)).first;
@@ -317,49 +312,24 @@ std::vector<at::Tensor> run_fused(const at::Device dev, int64_t bs, int64_t A, i
     if (!sb.clean) sb.t.zero_();                                       // the previous call on it did not complete
     sb.clean = false;
     arm(meta);
-    const int rc = launch(cap, hint | (seg_hint << 32) | (memo.small_boxes ? (int64_t(1) << 62) : 0), out.data_ptr<float>(), meta.p, meta.p + bs,
-                          ws.data_ptr(), (size_t)ws.numel(), sb.t.data_ptr(), (size_t)sb.t.numel(), stream.stream());
+    const int rc = launch(cap, api.obb_nms_obb_hints_word(&hints), out.data_ptr<float>(), meta.p, meta.p + bs, ws.data_ptr(), (size_t)ws.numel(),
+                          sb.t.data_ptr(), (size_t)sb.t.numel(), stream.stream());
     check(rc, "obb_non_max_suppression_obb");
     {
       py::gil_scoped_release nogil;
       wait_words(meta, stream);
     }
     sb.clean = true;                                                   // every launch of the call was made: its last kernel zeroes the counters
-    const int64_t st0 = meta.p[bs], st1 = meta.p[bs + 1];
-    seg_max = (st1 >> 32) & 0x1fffffffll;
-    memo.small_resolved = ((st1 >> 61) & 1) != 0;
-    cand_max = st1 & 0xffffffffll;
-    memo.small_boxes = ((st1 >> 62) & 1) != 0;
-    if (st0 == -1) {                                                   // a segment above the small kernel's limit: nothing is valid
-      memo.seg = std::max<int64_t>(seg_max, OBB_NMS_SMALL_SEG + 1);
-      memo.hold_seg = kHold;
-      continue;
+    switch (api.obb_nms_obb_hints_update(&hints, &cap, worst, meta.p, bs, meta.p + bs)) {
+      case OBB_HINTS_DONE: done = true; break;
+      case OBB_HINTS_RETRY: break;                                     // with the hints and the cap it updated
+      case OBB_HINTS_RETRY_SMALL_GRID:                                 // a team barrier of the NMS kernel timed out
+        if (retry.capped)
+          throw std::runtime_error("obb_non_max_suppression_obb: the NMS kernel aborted (a workgroup barrier timed out); results are invalid");
+        retry.cap();                                                   // once more with a grid that is resident under any CU mask
+        break;
     }
-    int64_t mn = 0;
-    for (int64_t b = 0; b < bs; b++) mn = std::min(mn, meta.p[b]);
-    if (mn < 0) {                                                      // a team barrier of the NMS kernel timed out
-      if (retry.capped)
-        throw std::runtime_error("obb_non_max_suppression_obb: the NMS kernel aborted (a workgroup barrier timed out); results are invalid");
-      retry.cap();                                                     // once more with a grid that is resident under any CU mask
-      continue;
-    }
-    if (st0 > cap) {                                                   // an image produced more candidates than slots
-      cap = std::min(worst, std::max<int64_t>(st0, 2 * cap));
-      continue;
-    }
-    if (hint > 0 && hint <= OBB_NMS_SORT_LDS_HINT && cand_max > OBB_NMS_SORT_LDS_MAX) {   // the hint undersold this batch: such images were left out
-      memo.cand = cand_max;
-      memo.hold_cand = kHold;
-      continue;
-    }
-    break;
   }
-  memo.cap = cap;
-  // hints of the next call, with hysteresis after a repeated call
-  if (memo.hold_cand > 0 && cand_max > OBB_NMS_SORT_LDS_HINT * 3 / 4) { memo.hold_cand--; memo.cand = std::max<int64_t>(cand_max, OBB_NMS_SORT_LDS_HINT + 1); }
-  else { memo.hold_cand = 0; memo.cand = cand_max; }
-  if (memo.hold_seg > 0 && (seg_max == 0 || seg_max > OBB_NMS_SMALL_SEG * 3 / 4)) { memo.hold_seg--; memo.seg = std::max<int64_t>(seg_max, OBB_NMS_SMALL_SEG + 1); }
-  else { memo.hold_seg = 0; memo.seg = seg_max; }                      // (0: the sort path of this call does not report it)
   result.reserve((size_t)bs);
   for (int64_t b = 0; b < bs; b++) result.push_back(view_of(out, b * max_det * 7, {meta.p[b], 7}, {7, 1}));
   return result;

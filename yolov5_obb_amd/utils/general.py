@@ -20,68 +20,67 @@ _POLL_SECONDS = 2e-3  # busy-poll this long (a bs16 step is ~0.2 ms), then yield
 _POLL_GIVE_UP = 1.0   # ... after this many seconds: fall back to a stream synchronise
 _MAX_NMS = 30000    # utils/general.py:794
 _CSL = 180          # utils/general.py:784
-_cap_memo = {}      # (device, thread, A, nc, multi_label, conf_thres) -> candidate slots per image that sufficed last time
 _ws_memo = {}       # (bs, cap, nc, agnostic, grid capped) -> workspace bytes (a ctypes call saved per batch)
 _meta_memo = {}     # (device index, bs, thread) -> the int64 buffer the counters are read back from
-_cand_memo = {}     # same key -> largest candidate count of an image in the previous call (sort-algorithm hint; 0 forces the generic sort)
-_SORT_LDS_HINT = 6144   # include/obb_hip.h OBB_NMS_SORT_LDS_HINT: hints up to this select the one-workgroup-per-image sort ...
-_SORT_LDS_MAX = 8192    # ... OBB_NMS_SORT_LDS_MAX: which takes at most this many candidates of an image
-_hold = {}              # (key, "seg" | "cand") -> calls the larger regime is still held after a repeated call (hysteresis)
-_HOLD = 8
-_seg_memo = {}          # same key -> largest NMS segment (an image's class) of the previous call: chooses the NMS kernel (the one-
-_SEG_SMALL = 384        # workgroup-per-segment kernel of csrc/nms_small.h takes segments up to this size; 0 = unknown: the persistent one)
+_SEG_SMALL = 384    # include/obb_hip.h OBB_NMS_SMALL_SEG: the one-workgroup-per-segment kernel of csrc/nms_small.h takes segments up to this size
+_HINTS_DONE, _HINTS_RETRY, _HINTS_RETRY_SMALL_GRID = 0, 1, 2   # include/obb_hip.h OBB_HINTS_*: what obb_nms_obb_hints_update answers
+_MAX_SHAPES = 512   # thread churn or a swept threshold must not grow a thread's hints without bound
+_tls = threading.local()   # .hints: (device, A, nc, multi_label, conf_thres) -> _lib.NmsObbHints of the calling thread: what its earlier
+                           # calls of that shape learned (include/obb_hip.h: obb_nms_obb_hints); other threads' batches say nothing about it
 
 
-_small_memo = {}        # same key -> the previous call met boxes with a sub-pixel side (status[1] bit 62): the next call runs k_tiny_cross
+def _hints_of(key, make=True):
+    hints = getattr(_tls, "hints", None)
+    if hints is None:
+        hints = _tls.hints = {}
+    h = hints.get(key)
+    if h is None and make:
+        if len(hints) >= _MAX_SHAPES:         # hints only: forgetting them costs the next call of every shape one repeated call at most
+            hints.clear()
+        h = hints[key] = _lib.NmsObbHints()
+        _lib.lib().obb_nms_obb_hints_init(C.byref(h))
+    return h
 
 
-_MEMO_LIMIT = 512       # keys (device, thread, shape, threshold): thread churn or a swept threshold must not grow the memos without bound
-
-
-def _key(dev_index, A, nc, multi, conf_thres):
-    # per device, calling thread and confidence threshold: other callers' batches say nothing about this one's
-    if len(_cap_memo) > _MEMO_LIMIT:          # hints only: forgetting them costs the next call of every shape one generic pass
-        for d in (_cap_memo, _cand_memo, _seg_memo, _hold, _small_memo):
-            d.clear()
-    return (dev_index, threading.get_ident(), int(A), int(nc), bool(multi), float(conf_thres))
+def _key(device, A, nc, multi, conf_thres):
+    idx = torch.device(device).index
+    return (torch.cuda.current_device() if idx is None else idx, int(A), int(nc), bool(multi), float(conf_thres))
 
 
 def hints_clear():
-    """Forget what earlier calls learned about their shapes (tests, tools)."""
-    for d in (_cap_memo, _cand_memo, _seg_memo, _hold, _small_memo):
-        d.clear()
+    """Forget what the calling thread's earlier calls learned about their shapes (tests, tools)."""
+    _tls.hints = {}
     ext = _lib.compiled()
     if ext is not None:
         ext.hints_clear()
 
 
 def hint_get(device, A, nc, multi_label, conf_thres):
-    """The hint state of a shape on the active binding: dict(cand=, seg=, cap=, small_boxes=) or None."""
-    idx = torch.device(device).index
-    idx = torch.cuda.current_device() if idx is None else idx
+    """The hint state of a shape on the active binding (the fields of obb_nms_obb_hints, include/obb_hip.h):
+    dict(cap=, cand=, seg=, hold_cand=, hold_seg=, small_boxes=, small_resolved=) or None."""
+    key = _key(device, A, nc, multi_label, conf_thres)
     ext = _lib.compiled()
     if ext is not None:
-        return ext.hint_get(idx, int(A), int(nc), bool(multi_label), float(conf_thres))
-    key = _key(idx, A, nc, multi_label, conf_thres)
-    if key not in _cand_memo and key not in _seg_memo:
+        return ext.hint_get(*key)
+    h = _hints_of(key, make=False)
+    if h is None:
         return None
-    return {"cand": _cand_memo.get(key, _SORT_LDS_HINT), "seg": _seg_memo.get(key, 1), "cap": _cap_memo.get(key, 0),
-            "small_boxes": bool(_small_memo.get(key, False)), "small_resolved": bool(_small_memo.get((key, "resolved"), False))}
+    return {"cap": h.cap, "cand": h.cand, "seg": h.seg, "hold_cand": h.hold_cand, "hold_seg": h.hold_seg,
+            "small_boxes": bool(h.small_boxes), "small_resolved": bool(h.small_resolved)}
 
 
 def hint_set(device, A, nc, multi_label, conf_thres, cand=None, seg=None):
     """Force the hints of the next call of a shape (cand = 0: the generic sort; seg = 1: the small-segment kernel)."""
-    idx = torch.device(device).index
-    idx = torch.cuda.current_device() if idx is None else idx
+    key = _key(device, A, nc, multi_label, conf_thres)
     ext = _lib.compiled()
     if ext is not None:
-        ext.hint_set(idx, int(A), int(nc), bool(multi_label), float(conf_thres), -1 if cand is None else int(cand), -1 if seg is None else int(seg))
+        ext.hint_set(*key, -1 if cand is None else int(cand), -1 if seg is None else int(seg))
         return
-    key = _key(idx, A, nc, multi_label, conf_thres)
+    h = _hints_of(key)
     if cand is not None:
-        _cand_memo[key] = int(cand); _hold[key, "cand"] = 0
+        h.cand, h.hold_cand = int(cand), 0
     if seg is not None:
-        _seg_memo[key] = int(seg); _hold[key, "seg"] = 0
+        h.seg, h.hold_seg = int(seg), 0
 
 
 def _label_rows(labels, bs, nc, device):
@@ -162,7 +161,7 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
     extra = _label_rows(labels, bs, nc, dev) if labels else None
     ext = _lib.compiled()
     if ext is not None:
-        # the compiled binding (csrc/torch_ext/nms_rotated_ext.cpp): the same call sequence, retries and hint memo as below, in C++
+        # the compiled binding (csrc/torch_ext/nms_rotated_ext.cpp): the call loop of _run_fused below, in C++
         cl = None
         if classes is not None:
             cl = [int(c) for c in (classes if isinstance(classes, (list, tuple)) else list(classes))]
@@ -208,11 +207,13 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
 
 def _run_fused(launch, dev, bs, A, nc, multi, conf_thres, n_extra, agn, max_det):
     """The ctypes binding's call loop around one fused entry (launch: obb_non_max_suppression_obb_col or _head): workspace,
-    polled counters, the retry cases of include/obb_hip.h and the hint memo of the shape."""
+    polled counters, and the shape's hints and retries as the library decides them (include/obb_hip.h: obb_nms_obb_hints_*)."""
     L = _lib.lib()
     worst = A * (nc if multi else 1) + n_extra
-    key = _key(dev.index, A, nc, multi, conf_thres)
-    cap = min(worst, max(_cap_memo.get(key, 0), 65536))
+    h = _hints_of((dev.index, A, nc, multi, float(conf_thres)))          # (_key of a tensor's device, spelled out)
+    hints = C.addressof(h)
+    cap = C.c_int64(L.obb_nms_obb_hints_cap(hints, worst))               # obb_nms_obb_hints_update may raise it: in / out
+    cap_p = C.addressof(cap)                                              # (plain addresses: the cheapest arguments ctypes takes)
     out = torch.empty((bs * max_det, 7), dtype=torch.float32, device=dev)   # packed: image b's rows follow image b-1's
     mkey = (dev.index, bs, threading.get_ident())
     meta = _meta_memo.get(mkey)                                       # counts[bs] + status[2]: read back before returning,
@@ -223,27 +224,20 @@ def _run_fused(launch, dev, bs, A, nc, multi, conf_thres, n_extra, agn, max_det)
         meta = torch.empty(bs + 2, dtype=torch.int64).pin_memory()
         _meta_memo[mkey] = meta = (meta, meta.numpy())
     meta, meta_np = meta
+    counts_p = meta.data_ptr()
+    status_p = counts_p + 8 * bs
     capped = False                # obb_nms_set_max_grid is per calling thread (thread_local in the library): no other thread sees it
     try:
         while True:
-            # no history for this shape: assume the regime of the reference's default thresholds (at most a few thousand
-            # candidates per image: the one-workgroup-per-image sort); a batch that turns out larger reports it (status[1]) and is
-            # run once more on the multi-workgroup sort, which the memo then selects directly -- the first call of a shape is the fast
-            # path, not the slow one (round 3 started from hint 0 = the generic sort)
-            hint = int(_cand_memo.get(key, _SORT_LDS_HINT))
-            # the same for the NMS kernel: assume the small segments of that regime (a few hundred boxes per image and class);
-            # a call that meets a larger one reports it (status[0] = -1) and is repeated on the persistent kernel
-            seg_hint = int(_seg_memo.get(key, 1))
             meta_np.fill(_PENDING)
             with _lib.guard(dev):
                 st = _lib.stream_handle(dev)
-                wkey = (bs, cap, nc, agn, capped)          # (the library sizes the workspace from the calling thread's grid cap)
+                wkey = (bs, cap.value, nc, agn, capped)    # (the library sizes the workspace from the calling thread's grid cap)
                 nbytes = _ws_memo.get(wkey)
                 if nbytes is None:
-                    nbytes = _ws_memo[wkey] = L.obb_nms_obb_workspace_bytes(bs, cap, nc, agn)
+                    nbytes = _ws_memo[wkey] = L.obb_nms_obb_workspace_bytes(bs, cap.value, nc, agn)
                 ws = _lib.workspace(nbytes, dev, st)
-                rc = launch(cap, (hint & 0xffffffff) | ((seg_hint & 0x1fffffff) << 32) | ((1 << 62) if _small_memo.get(key) else 0),
-                            _lib.ptr(out), _lib.ptr(meta), C.c_void_p(meta.data_ptr() + 8 * bs), ws, st)
+                rc = launch(cap.value, L.obb_nms_obb_hints_word(hints), _lib.ptr(out), counts_p, status_p, ws, st)
             _lib.check(rc, "obb_non_max_suppression_obb")
             t_poll = time.perf_counter()                              # every entry is one aligned 8-byte store of the last kernel
             while meta_np.min() == _PENDING:
@@ -253,46 +247,16 @@ def _run_fused(launch, dev, bs, A, nc, multi, conf_thres, n_extra, agn, max_det)
                     break
                 if waited > _POLL_SECONDS:                            # the stream still holds earlier work (the model's forward):
                     time.sleep(0)                                     # let other Python threads (DataLoader, pin-memory) run
-            m = meta_np.tolist()
-            _small_memo[key] = bool((m[bs + 1] >> 62) & 1)                    # status[1]: bit 62 = boxes with a sub-pixel side were met,
-            _small_memo[key, "resolved"] = bool((m[bs + 1] >> 61) & 1)        # bit 61 = ... and such an image kept its class segments
-            seg_max, m[bs + 1] = (m[bs + 1] >> 32) & 0x1fffffff, m[bs + 1] & 0xffffffff       # largest segment | largest candidate count
-            if m[bs] == -1:                                           # a segment above the small kernel's limit: nothing is valid
-                _seg_memo[key] = max(int(seg_max), _SEG_SMALL + 1)
-                _hold[key, "seg"] = _HOLD
-                continue
-            if min(m[:bs]) < 0:                                       # a team barrier of the NMS kernel timed out
+            action = L.obb_nms_obb_hints_update(hints, cap_p, worst, counts_p, bs, status_p)
+            if action == _HINTS_DONE:
+                break
+            if action == _HINTS_RETRY_SMALL_GRID:                     # a team barrier of the NMS kernel timed out
                 if capped:
-                    _lib.checked_count(min(m[:bs]), "obb_non_max_suppression_obb")
+                    _lib.checked_count(int(meta_np[:bs].min()), "obb_non_max_suppression_obb")
                 capped = True
                 L.obb_nms_set_max_grid(8)                             # once more with a grid that is resident under any CU mask
-                continue
-            if m[bs] > cap:                                           # an image produced more candidates than slots
-                cap = min(worst, max(int(m[bs]), 2 * cap))
-                continue
-            if 0 < hint <= _SORT_LDS_HINT and m[bs + 1] > _SORT_LDS_MAX:   # the hint undersold this batch: such images were left out
-                _cand_memo[key] = int(m[bs + 1])
-                _hold[key, "cand"] = _HOLD
-                continue
-            break
     finally:
         if capped:
             L.obb_nms_set_max_grid(0)
-    _cap_memo[key] = cap
-    # the hints of the next call.  After a repeated call the larger regime is held for _HOLD calls unless the batch falls clearly
-    # (25 %) below the limit: a stream whose batches hover around a limit does not pay the repeat on every other batch
-    cand, seg = int(m[bs + 1]), int(seg_max)                          # (seg 0: the sort path of this call does not report it)
-    if _hold.get((key, "cand"), 0) > 0 and cand > _SORT_LDS_HINT * 3 // 4:
-        _hold[key, "cand"] -= 1
-        cand = max(cand, _SORT_LDS_HINT + 1)
-    else:
-        _hold[key, "cand"] = 0
-    if _hold.get((key, "seg"), 0) > 0 and (seg == 0 or seg > _SEG_SMALL * 3 // 4):
-        _hold[key, "seg"] -= 1
-        seg = max(seg, _SEG_SMALL + 1)
-    else:
-        _hold[key, "seg"] = 0
-    _cand_memo[key] = cand
-    _seg_memo[key] = seg
-    counts = m[:bs]
+    counts = meta_np[:bs].tolist()
     return list(out.narrow(0, 0, sum(counts)).split_with_sizes(counts))     # one call instead of bs slicing ops
