@@ -19,6 +19,7 @@
 #include "detect_math.h"
 #include "confusion_math.h"
 #include "geom.h"
+#include "ws_layout.h"
 
 namespace obb {
 
@@ -860,7 +861,7 @@ __global__ __launch_bounds__(kVoThreads) void k_vo_match(const float* __restrict
 // atomic per non-zero cell, when (nc + 1)^2 <= kCmHistLds (nc <= 109); else global atomics directly.  Per-image counts < 2^32.
 constexpr int kCmThreads = 1024;
 constexpr int kCmHistLds = 110 * 110;      // 48,400 B beside the 14 KiB of label tile and slots: 61.4 KiB, two workgroups in a CU's 160 KiB
-struct CmWs {                              // the call's workspace, carved by cm_carve (labels by position, detections by packed row)
+struct CmWs {                              // the call's workspace, laid out by cm_layout (labels by position, detections by packed row)
   unsigned long long* win;                 // [nt] winner slot per label
   float* lbox; int* lcls;                  // [nt][4], [nt] class index or -1
   float* dbox; int* dcls;                  // [n][4], [n] class index or -1
@@ -1042,9 +1043,17 @@ int obb_val_postprocess_f32(const float* det7, int64_t n, float pad_x, float pad
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 
-size_t obb_val_tail_batch_workspace_bytes(int64_t n_det, int64_t nt) {
-  return (size_t)(n_det > 0 ? n_det : 1) * 8 + (size_t)(nt > 0 ? nt : 1) * 20 + 512;
+// the workspace of the val tail: the match arrays of k_vt_dets and k_vt_stats' arrival counter (nothing in it grows with nt)
+struct VtWs { int* best_label; float* best_iou; int* counter; size_t bytes; };
+static VtWs vt_layout(void* base, int64_t n) {
+  const size_t nn = (size_t)(n > 0 ? n : 0);
+  obb::WsCursor c(base);
+  VtWs w;
+  w.best_label = c.take<int>(nn); w.best_iou = c.take<float>(nn); w.counter = c.take<int>(1);
+  w.bytes = c.total();
+  return w;
 }
+size_t obb_val_tail_batch_workspace_bytes(int64_t n_det, int64_t nt) { (void)nt; return vt_layout(nullptr, n_det).bytes; }
 
 // the per-image table of a batch call from its host arrays (det_row_host NULL: packed detections); OBB_ERR_BAD_ARG when they are inconsistent
 static int vt_fill_imgs(obb::ValTailImgs& im, const int64_t* det_row_host, const int64_t* det_off_host, int64_t bs, const float* img5_host) {
@@ -1079,14 +1088,12 @@ static int val_tail_batch_impl(const float* det7, const int64_t* det_row_host, c
   const int64_t n = det_off_host[bs];
   if (n == 0) { if (done) *done = 0; return OBB_OK; }            // (host-visible memory: nothing to wait for)
   if (!det7 || !stats) return OBB_ERR_BAD_ARG;
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < obb_val_tail_batch_workspace_bytes(n, nt)) return OBB_ERR_WORKSPACE;
+  const VtWs w = vt_layout(ws, n);
+  if (!obb::ws_ok(ws, ws_bytes, w.bytes)) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  int* best_label = (int*)ws;
-  float* best_iou = (float*)(best_label + n);
-  int* counter = (int*)(((uintptr_t)(best_iou + n) + 255) & ~(uintptr_t)255);              // (inside the 512 spare bytes)
   obb::k_vt_dets<<<(unsigned)((n + 127) / 128), 128, 0, st>>>(det7, (int)n, im, targets, (int)nt, (int)tcols, iouv, poly10, hbb6, polyn10, hbbn6,
-                                                            best_label, best_iou, counter);
-  obb::k_vt_stats<float><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(det7, best_label, best_iou, im, iouv, (int)n, niou, stats, counter,
+                                                            w.best_label, w.best_iou, w.counter);
+  obb::k_vt_stats<float><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(det7, w.best_label, w.best_iou, im, iouv, (int)n, niou, stats, w.counter,
                                                               reinterpret_cast<long long*>(done));
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
@@ -1114,21 +1121,28 @@ int obb_val_tail_batch_rows_f32(const float* det7, const int64_t* det_row_host, 
                              ws, ws_bytes, stream, done);
 }
 
-size_t obb_process_batch_workspace_bytes(int64_t n, int64_t m) { return (size_t)(n > 0 ? n : 1) * 8 + (size_t)(m > 0 ? m : 1) * 4 + 256; }
+struct PbWs { int* best_label; float* best_iou; int* winner; size_t bytes; };
+static PbWs pb_layout(void* base, int64_t n, int64_t m) {
+  const size_t nn = (size_t)(n > 0 ? n : 0);
+  obb::WsCursor c(base);
+  PbWs w;
+  w.best_label = c.take<int>(nn); w.best_iou = c.take<float>(nn); w.winner = c.take<int>((size_t)(m > 0 ? m : 1));   // (m == 0: one slot is still set)
+  w.bytes = c.total();
+  return w;
+}
+size_t obb_process_batch_workspace_bytes(int64_t n, int64_t m) { return pb_layout(nullptr, n, m).bytes; }
 
 int obb_process_batch_f32(const float* det6, int64_t n, const float* lab5, int64_t m, const float* iouv, int niou, uint8_t* correct,
                           void* ws, size_t ws_bytes, void* stream) {
   if (n < 0 || m < 0 || niou < 1 || n > 0x7fffffff || m > 0x7fffffff) return OBB_ERR_BAD_ARG;
   if (n == 0) return OBB_OK;
   if (!det6 || !iouv || !correct || (m > 0 && !lab5)) return OBB_ERR_BAD_ARG;
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < obb_process_batch_workspace_bytes(n, m)) return OBB_ERR_WORKSPACE;
+  const PbWs w = pb_layout(ws, n, m);
+  if (!obb::ws_ok(ws, ws_bytes, w.bytes)) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  int* best_label = (int*)ws;
-  float* best_iou = (float*)(best_label + n);
-  int* winner = (int*)(best_iou + n);
-  if (hipMemsetAsync(winner, 0x7f, (size_t)(m > 0 ? m : 1) * 4, st) != hipSuccess) return OBB_ERR_LAUNCH;
-  obb::k_pb_best<<<(unsigned)((n + 127) / 128), 128, 0, st>>>(det6, (int)n, lab5, (int)m, iouv, best_label, best_iou, winner);
-  obb::k_pb_correct<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(best_label, best_iou, winner, iouv, (int)n, niou, correct);
+  if (hipMemsetAsync(w.winner, 0x7f, (size_t)(m > 0 ? m : 1) * 4, st) != hipSuccess) return OBB_ERR_LAUNCH;
+  obb::k_pb_best<<<(unsigned)((n + 127) / 128), 128, 0, st>>>(det6, (int)n, lab5, (int)m, iouv, w.best_label, w.best_iou, w.winner);
+  obb::k_pb_correct<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(w.best_label, w.best_iou, w.winner, iouv, (int)n, niou, correct);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 
@@ -1155,23 +1169,20 @@ int obb_val_tail_batch_obb_f32(const float* det7, const int64_t* det_row_host, c
   return obb::vo_launch<true, float>(det7, n, im, targets, nt, tcols, iouv, niou, stats, match_label, match_iou, stream);
 }
 
-size_t obb_confusion_workspace_bytes(int64_t n_det, int64_t nt) {
-  return (size_t)(n_det > 0 ? n_det : 1) * 28 + (size_t)(nt > 0 ? nt : 1) * 28 + 256;
+// the arrays of obb::CmWs: one block each
+struct CmLayout { obb::CmWs w; size_t bytes; };
+static CmLayout cm_layout(void* base, int64_t n, int64_t nt) {
+  const size_t nn = (size_t)(n > 0 ? n : 0), ll = (size_t)(nt > 0 ? nt : 0);
+  obb::WsCursor c(base);
+  CmLayout l;
+  l.w.win = c.take<unsigned long long>(ll);
+  l.w.lbox = c.take<float>(4 * ll); l.w.lcls = c.take<int>(ll);
+  l.w.dbox = c.take<float>(4 * nn); l.w.dcls = c.take<int>(nn);
+  l.w.biou = c.take<float>(nn); l.w.blab = c.take<int>(nn);
+  l.bytes = c.total();
+  return l;
 }
-
-// the arrays of obb::CmWs in a workspace of obb_confusion_workspace_bytes(n, nt) bytes (the 8-byte slots first, on an 8-byte boundary)
-static obb::CmWs cm_carve(void* ws, int64_t n, int64_t nt) {
-  const size_t nn = (size_t)(n > 0 ? n : 1), ll = (size_t)(nt > 0 ? nt : 1);
-  obb::CmWs w;
-  w.win = (unsigned long long*)(((uintptr_t)ws + 7) & ~(uintptr_t)7);
-  w.lbox = (float*)(w.win + ll);
-  w.lcls = (int*)(w.lbox + 4 * ll);
-  w.dbox = (float*)(w.lcls + ll);
-  w.dcls = (int*)(w.dbox + 4 * nn);
-  w.biou = (float*)(w.dcls + nn);
-  w.blab = (int*)(w.biou + nn);
-  return w;
-}
+size_t obb_confusion_workspace_bytes(int64_t n_det, int64_t nt) { return cm_layout(nullptr, n_det, nt).bytes; }
 
 int obb_confusion_batch_f32(const float* det7, const int64_t* det_off_host, int64_t bs, const float* targets, int64_t nt, int64_t tcols,
                             const float* img5_host, int nc, float conf_thres, float iou_thres, int64_t* matrix_i64, void* ws,
@@ -1184,9 +1195,10 @@ int obb_confusion_batch_f32(const float* det7, const int64_t* det_off_host, int6
   const int64_t n = det_off_host[bs];
   if (n == 0 || nt == 0) return OBB_OK;                          // no image has both detections and labels: nothing is counted
   if (!det7) return OBB_ERR_BAD_ARG;
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < obb_confusion_workspace_bytes(n, nt)) return OBB_ERR_WORKSPACE;
+  const CmLayout l = cm_layout(ws, n, nt);
+  if (!obb::ws_ok(ws, ws_bytes, l.bytes)) return OBB_ERR_WORKSPACE;
   obb::k_confusion<true><<<(unsigned)bs, obb::kCmThreads, 0, (hipStream_t)stream>>>(
-      det7, im, 0, targets, (int)nt, (int)tcols, nc, conf_thres, iou_thres, reinterpret_cast<unsigned long long*>(matrix_i64), cm_carve(ws, n, nt));
+      det7, im, 0, targets, (int)nt, (int)tcols, nc, conf_thres, iou_thres, reinterpret_cast<unsigned long long*>(matrix_i64), l.w);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 
@@ -1195,10 +1207,11 @@ int obb_confusion_process_batch_f32(const float* det6, int64_t n, const float* l
   if (n < 0 || m < 0 || n > 0x7fffffff || m > 0x7fffffff || nc < 1 || nc > 32767 || !matrix_i64) return OBB_ERR_BAD_ARG;
   if (n == 0 || m == 0) return OBB_OK;
   if (!det6 || !lab5) return OBB_ERR_BAD_ARG;
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < obb_confusion_workspace_bytes(n, m)) return OBB_ERR_WORKSPACE;
+  const CmLayout l = cm_layout(ws, n, m);
+  if (!obb::ws_ok(ws, ws_bytes, l.bytes)) return OBB_ERR_WORKSPACE;
   obb::ValTailImgs im = {};                                      // (not read by the one-image form)
   obb::k_confusion<false><<<1, obb::kCmThreads, 0, (hipStream_t)stream>>>(
-      det6, im, (int)n, lab5, (int)m, 5, nc, conf_thres, iou_thres, reinterpret_cast<unsigned long long*>(matrix_i64), cm_carve(ws, n, m));
+      det6, im, (int)n, lab5, (int)m, 5, nc, conf_thres, iou_thres, reinterpret_cast<unsigned long long*>(matrix_i64), l.w);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 

@@ -27,6 +27,7 @@
 #include "obb_hip.h"
 #include "dtype_device.h"
 #include "loss_math.h"
+#include "ws_layout.h"
 
 namespace obb {
 
@@ -531,8 +532,6 @@ __global__ __launch_bounds__(256) void k_loss_entries_bwd(const LossDev* __restr
 }
 
 // ------------------------------------------------------------------ host side
-static inline size_t al(size_t v) { return (v + 255) / 256 * 256; }
-
 struct LossCarve {
   LossDev* dev;
   int* counts; int* head; int *e_cell, *e_t, *e_ao, *prev; float4* e_tbox;
@@ -555,24 +554,25 @@ static int loss_check(const obb_loss_config* c, int64_t nt) {
   return OBB_OK;
 }
 
-static void loss_carve(void* base, const obb_loss_config* c, int64_t nt, LossCarve* cv) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += al(bytes ? bytes : 16); return base ? (char*)base + o : (char*)nullptr; };
+static LossCarve loss_carve(void* base, const obb_loss_config* c, int64_t nt) {
+  LossCarve cv;
+  WsCursor w(base);
   long long tot = 0;
   for (int i = 0; i < c->nl; i++) tot += (long long)c->bs * c->na * c->ny[i] * c->nx[i];
-  const size_t ce = (size_t)5 * c->na * (size_t)nt * c->nl;
-  cv->dev = (LossDev*)take(sizeof(LossDev));
-  cv->counts = (int*)take((kLv + 2) * 4);      // [kLv] entries per level | bad-target flag | finalize ticket
-  cv->head_bytes = (size_t)tot * 4;
-  cv->head = (int*)take(cv->head_bytes);
-  cv->e_cell = (int*)take(ce * 4); cv->e_t = (int*)take(ce * 4); cv->e_ao = (int*)take(ce * 4); cv->prev = (int*)take(ce * 4);
-  cv->e_tbox = (float4*)take(ce * 16);
-  cv->part_box = (float*)take(ce * 4); cv->part_cls = (float*)take(ce * 4); cv->part_th = (float*)take(ce * 4); cv->part_obj = (float*)take(ce * 4);
-  cv->dense_part = (double*)take((size_t)kLv * kDenseBlocks * 8);
-  cv->objcol = (float*)take((size_t)tot * 4);
-  cv->lvl_out = (float*)take(kLv * 4 * 4);
-  cv->blkcnt = (int*)take(((size_t)5 * c->na * (size_t)nt / 1024 + 2) * c->nl * 4);
-  cv->total = off;
+  const size_t ce = (size_t)5 * c->na * (size_t)nt * c->nl;   // (0 without targets: an empty take is still a block)
+  cv.dev = w.take<LossDev>(1);
+  cv.counts = w.take<int>(kLv + 2);           // [kLv] entries per level | bad-target flag | finalize ticket
+  cv.head_bytes = (size_t)tot * 4;
+  cv.head = w.take<int>((size_t)tot);
+  cv.e_cell = w.take<int>(ce); cv.e_t = w.take<int>(ce); cv.e_ao = w.take<int>(ce); cv.prev = w.take<int>(ce);
+  cv.e_tbox = w.take<float4>(ce);
+  cv.part_box = w.take<float>(ce); cv.part_cls = w.take<float>(ce); cv.part_th = w.take<float>(ce); cv.part_obj = w.take<float>(ce);
+  cv.dense_part = w.take<double>((size_t)kLv * kDenseBlocks);
+  cv.objcol = w.take<float>((size_t)tot);
+  cv.lvl_out = w.take<float>(kLv * 4);
+  cv.blkcnt = w.take<int>(((size_t)5 * c->na * (size_t)nt / 1024 + 2) * c->nl);
+  cv.total = w.total();
+  return cv;
 }
 
 static void loss_fill(LossDev& d, const obb_loss_config* c, const LossCarve& cv, const float* targets, int64_t nt, int64_t tcols) {
@@ -625,10 +625,7 @@ using namespace obb;
 extern "C" {
 
 size_t obb_loss_workspace_bytes(const obb_loss_config* cfg, int64_t nt) {
-  if (loss_check(cfg, nt)) return 0;
-  LossCarve cv;
-  loss_carve(nullptr, cfg, nt, &cv);
-  return cv.total;
+  return loss_check(cfg, nt) ? 0 : loss_carve(nullptr, cfg, nt).total;
 }
 
 int obb_loss_build_targets(const obb_loss_config* cfg, const float* targets, int64_t nt, int64_t tcols, int32_t* counts_out,
@@ -636,9 +633,8 @@ int obb_loss_build_targets(const obb_loss_config* cfg, const float* targets, int
   int rc = loss_check(cfg, nt);
   if (rc) return rc;
   if ((nt > 0 && !targets) || (nt > 0 && tcols < 7) || !counts_out) return OBB_ERR_BAD_ARG;
-  LossCarve cv;
-  loss_carve(ws, cfg, nt, &cv);
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  const LossCarve cv = loss_carve(ws, cfg, nt);
+  if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   LossDev d;
   loss_fill(d, cfg, cv, targets, nt, tcols);
@@ -655,9 +651,8 @@ int obb_loss_export_targets(const obb_loss_config* cfg, int64_t nt, int level, i
   if (level < 0 || level >= cfg->nl || n < 0 || n > 5LL * cfg->na * nt) return OBB_ERR_BAD_ARG;
   if (n == 0) return OBB_OK;
   if (!indices4 || !tbox4 || !anch2 || !tcls || !csl180) return OBB_ERR_BAD_ARG;
-  LossCarve cv;
-  loss_carve(ws, cfg, nt, &cv);
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  const LossCarve cv = loss_carve(ws, cfg, nt);
+  if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
   k_bt_export<<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(cv.dev, level, (int)n, indices4, tbox4, anch2, tcls, csl180);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
@@ -668,9 +663,8 @@ int obb_loss_forward(const obb_loss_config* cfg, const void* const* p_levels_hos
   if (rc) return rc;
   if (!p_levels_host || !loss_out || (nt > 0 && !targets) || (nt > 0 && tcols < 7) || !dtype_known(dtype))
     return OBB_ERR_BAD_ARG;
-  LossCarve cv;
-  loss_carve(ws, cfg, nt, &cv);
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  const LossCarve cv = loss_carve(ws, cfg, nt);
+  if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   LossDev d;
   loss_fill(d, cfg, cv, targets, nt, tcols);
@@ -691,9 +685,8 @@ int obb_loss_backward(const obb_loss_config* cfg, const void* const* p_levels_ho
   int rc = loss_check(cfg, nt);
   if (rc) return rc;
   if (!p_levels_host || !grad_levels_host || !grad_scale || (nt > 0 && !targets) || !dtype_known(dtype)) return OBB_ERR_BAD_ARG;
-  LossCarve cv;
-  loss_carve(ws, cfg, nt, &cv);
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  const LossCarve cv = loss_carve(ws, cfg, nt);
+  if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   LossDev d;
   loss_fill(d, cfg, cv, targets, nt, tcols);     // entries / counts / head in `ws` are the ones obb_loss_forward left there

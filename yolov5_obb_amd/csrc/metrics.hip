@@ -16,6 +16,7 @@
 
 #include "ap_math.h"
 #include "obb_hip.h"
+#include "ws_layout.h"
 
 namespace obb {
 namespace {
@@ -40,22 +41,20 @@ struct ApWs {
   size_t bytes;
 };
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-ApWs ap_layout(char* base, int64_t n, int niou, int nc_max) {
+ApWs ap_layout(void* base, int64_t n, int niou, int nc_max) {
   const size_t rows = (size_t)(n > 0 ? n : 1), tiles = rows / kApTile + (size_t)nc_max;
   ApWs w;
-  size_t o = 0;
-  w.key = (unsigned long long*)(base + o); o += up256(rows * 8);
-  w.idx = (int*)(base + o); o += up256(rows * 4);
-  w.tpc = (int*)(base + o); o += up256(rows * niou * 4);
-  w.env = (double*)(base + o); o += up256(rows * niou * 8);
-  w.tile_tp = (int*)(base + o); o += up256(tiles * niou * 4);
-  w.tile_max = (double*)(base + o); o += up256(tiles * niou * 8);
-  w.seg_off = (int*)(base + o); o += up256((size_t)(nc_max + 1) * 4);
-  w.tile_start = (int*)(base + o); o += up256((size_t)(nc_max + 1) * 4);
-  w.curves = (double*)(base + o); o += up256((size_t)3 * nc_max * kApPx * 8);
-  w.bytes = o;
+  WsCursor c(base);
+  w.key = c.take<unsigned long long>(rows);
+  w.idx = c.take<int>(rows);
+  w.tpc = c.take<int>(rows * niou);
+  w.env = c.take<double>(rows * niou);
+  w.tile_tp = c.take<int>(tiles * niou);
+  w.tile_max = c.take<double>(tiles * niou);
+  w.seg_off = c.take<int>((size_t)nc_max + 1);
+  w.tile_start = c.take<int>((size_t)nc_max + 1);
+  w.curves = c.take<double>((size_t)3 * nc_max * kApPx);
+  w.bytes = c.total();
   return w;
 }
 
@@ -449,9 +448,9 @@ int obb_ap_per_class_f32(const float* stats, int64_t row_stride, int64_t n, int 
   if (n < 0 || n >= 0x7fffffffLL || m < 0 || m >= 0x7fffffffLL || niou < 1 || niou > kApMaxIou || nc_max < 1 || nc_max > kApMaxNc)
     return OBB_ERR_BAD_ARG;
   if (!ap || !prf || !counts || !info || (n > 0 && (!stats || row_stride < niou + 2)) || (m > 0 && !target_cls)) return OBB_ERR_BAD_ARG;
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < obb_ap_per_class_workspace_bytes(n, niou, nc_max)) return OBB_ERR_WORKSPACE;
+  const ApWs w = ap_layout(ws, n, niou, nc_max);
+  if (!ws_ok(ws, ws_bytes, w.bytes)) return OBB_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const ApWs w = ap_layout((char*)ws, n, niou, nc_max);
   double* cur = curves ? curves : w.curves;
   if (hipMemsetAsync(ap, 0, (size_t)nc_max * niou * 8, st) != hipSuccess || hipMemsetAsync(prf, 0, (size_t)nc_max * 5 * 8, st) != hipSuccess ||
       hipMemsetAsync(counts, 0, (size_t)nc_max * 2 * 4, st) != hipSuccess || hipMemsetAsync(info, 0, 16, st) != hipSuccess ||

@@ -22,6 +22,7 @@
 #include "psrs_sort.h"
 #include "nms_small.h"
 #include "segsort.h"
+#include "ws_layout.h"
 
 namespace obb {
 
@@ -424,9 +425,7 @@ __global__ void k_finalize(const int* __restrict__ keep_cnt, const int* __restri
   }
 }
 
-// ---------------------------------------------------------------- workspace
-static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
+// ---------------------------------------------------------------- workspace (ws_layout.h)
 // Chunk capacities: the first chunk has 2048 boxes, later chunks double up to 8192 for a single list, 2048 per segment for
 // batches of up to 64 segments and 1024 beyond.  (The edge list of a team is sized for the worst case cap*(cap-1)/2 of one
 // chunk: 134 MB at 8192, 8.4 MB at 2048, 2 MB at 1024 -- times the number of teams.)
@@ -438,7 +437,7 @@ constexpr int kMaxTeams = 1024;     // >= number of CUs of any gfx950 part
 struct Carve {
   unsigned long long *keys_a, *keys_b;
   uint32_t *vals_a, *vals_b;
-  void* sort_tmp; size_t sort_tmp_bytes;
+  void* sort_tmp; size_t sort_tmp_bytes; uint32_t* sort_hist;
   float4* rec; u64* alive; size_t alive_bytes;
   int *seg_begin, *seg_end, *keep_cnt;
   int* bar; size_t bar_bytes;          // team barrier counters, abort flag, per-team nrows / nedges (zeroed before every launch)
@@ -448,7 +447,7 @@ struct Carve {
   uint32_t *rows, *edges;
   long long ecap;
   GridDev grid;                        // spatial index (rotated boxes, single list); grid.meta == NULL: not carved
-  // the phase-kernel path of a long single list (nms_mk.h); mk_cidx == NULL: not carved.  Its control block is the head of `bar`.
+  // the phase-kernel path of a long single list (nms_mk.h); mk_cidx == NULL: not carved.  Its control block mk_ctl is a block of its own.
   int* mk_ctl; uint32_t* mk_cidx; float4* mk_ent; uint16_t* mk_start; u64* mk_kbits; uint4* mk_pend1; uint8_t* mk_hasin; u64* tstart;   // mk_ctl: 1 KB (control block, edge counter at int 64)
   size_t grid_zero_bytes;              // GridMeta + slot counters: one contiguous block, zeroed before every build
   size_t total;
@@ -486,79 +485,75 @@ static int hw_cu_count() {
   return cus;
 }
 
-// scratch of the sorts: samples + cut table of the three-launch sort (psrs_sort.h), tile histograms of the radix sort (segsort.h)
-static size_t sort_tmp_bytes_for(size_t n) {
-  return align_up(ps_scratch_bytes()) + (((n + kSrsTile - 1) / kSrsTile) + 1) * 256 * 4;
-}
-
-static int carve(void* base, int64_t n, int64_t nseg, int recq, int C, Carve* cv) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return base ? (char*)base + o : (char*)nullptr; };
+static Carve carve(void* base, int64_t n, int64_t nseg, int recq, int C) {
+  Carve cv{};                            // (grid.meta, mk_*: NULL unless carved below)
+  WsCursor w(base);
   size_t nn = (size_t)(n > 0 ? n : 1), ns = (size_t)(nseg > 0 ? nseg : 1);
-  cv->keys_a = (unsigned long long*)take(nn * 8); cv->keys_b = (unsigned long long*)take(nn * 8);
-  cv->vals_a = (uint32_t*)take(nn * 4); cv->vals_b = (uint32_t*)take(nn * 4);
-  cv->sort_tmp_bytes = sort_tmp_bytes_for(nn);
-  cv->sort_tmp = take(cv->sort_tmp_bytes);
-  cv->rec = (float4*)take(nn * recq * 16);
-  cv->alive_bytes = (nn / 64 + 10) * 8;      // + guard words (zeroed by the prep kernels)
-  cv->alive = (u64*)take(cv->alive_bytes);
-  cv->bar_bytes = ((size_t)kMaxTeams * 128 + 64 + 2 * (size_t)kMaxTeams + 2 * (size_t)kBarGroups * 64) * 4;   // (+ the group counters of the two grid-wide barriers)
-  cv->bar = (int*)take(cv->bar_bytes);
-  cv->abort_flag = cv->bar + (size_t)kMaxTeams * 128;
-  cv->nrows = cv->abort_flag + 64;
-  cv->nedges = cv->nrows + kMaxTeams;
-  cv->prof = (u64*)take(56 * 8);
-  cv->tstart = (u64*)take(64);
-  cv->plan = (int4*)take((size_t)kMaxTeams * 16);
-  cv->seg_begin = (int*)take(ns * 4); cv->seg_end = (int*)take(ns * 4);
-  cv->keep_cnt = (int*)take(ns * 4);
+  cv.keys_a = w.take<unsigned long long>(nn); cv.keys_b = w.take<unsigned long long>(nn);
+  cv.vals_a = w.take<uint32_t>(nn); cv.vals_b = w.take<uint32_t>(nn);
+  // scratch of the sorts: samples + cut table of the three-launch sort (psrs_sort.h), tile histograms of the radix sort (segsort.h)
+  cv.sort_tmp_bytes = ps_scratch_bytes();
+  cv.sort_tmp = w.bytes(cv.sort_tmp_bytes);
+  cv.sort_hist = w.take<uint32_t>((((nn + kSrsTile - 1) / kSrsTile) + 1) * 256);
+  cv.rec = w.take<float4>(nn * recq);
+  cv.alive_bytes = (nn / 64 + 10) * 8;      // + guard words (zeroed by the prep kernels)
+  cv.alive = (u64*)w.bytes(cv.alive_bytes);
+  cv.bar_bytes = ((size_t)kMaxTeams * 128 + 64 + 2 * (size_t)kMaxTeams + 2 * (size_t)kBarGroups * 64) * 4;   // (+ the group counters of the two grid-wide barriers)
+  cv.bar = (int*)w.bytes(cv.bar_bytes);
+  if (cv.bar) { cv.abort_flag = cv.bar + (size_t)kMaxTeams * 128; cv.nrows = cv.abort_flag + 64; cv.nedges = cv.nrows + kMaxTeams; }
+  cv.prof = w.take<u64>(56); cv.tstart = w.take<u64>(8); cv.plan = w.take<int4>(kMaxTeams);
+  cv.seg_begin = w.take<int>(ns); cv.seg_end = w.take<int>(ns); cv.keep_cnt = w.take<int>(ns);
   // scratch that only the segment a team is working on needs: one copy per team, not per segment
   size_t nteams = ns < (size_t)cu_count() ? ns : (size_t)cu_count();
-  cv->rows = (uint32_t*)take((nn + 64 * kMaxSlabs) * 4);      // (+ the padding of the slab-major layout)
-  cv->ecap = (long long)C * (C - 1) / 2; if (cv->ecap < 1) cv->ecap = 1;
-  cv->edges = (uint32_t*)take(nteams * (size_t)cv->ecap * 4);
-  cv->grid = GridDev{}; cv->grid_zero_bytes = 0;
-  cv->mk_ctl = nullptr; cv->mk_cidx = nullptr; cv->mk_ent = nullptr; cv->mk_start = nullptr; cv->mk_kbits = nullptr; cv->mk_pend1 = nullptr; cv->mk_hasin = nullptr;
+  cv.rows = w.take<uint32_t>(nn + 64 * kMaxSlabs);            // (+ the padding of the slab-major layout)
+  cv.ecap = (long long)C * (C - 1) / 2; if (cv.ecap < 1) cv.ecap = 1;
+  cv.edges = w.take<uint32_t>(nteams * (size_t)cv.ecap);
   if (recq == RotGeom::RECQ && nseg == 1 && n >= kGridMinN) {
     const uint32_t M = grid_slots(n);
-    cv->grid.mask = M - 1;
-    const size_t slab_tot_bytes = (size_t)(1 + kMaxTeams / 16) * kMaxSlabs * 4;   // slab totals + group totals (slab_setup)
-    const size_t slab_zero = align_up((size_t)kSlabCopies * kSlabWords * 4 + 64) + align_up(slab_tot_bytes);
-    cv->grid_zero_bytes = align_up(sizeof(GridMeta)) + slab_zero + ((size_t)M + 4) * 4;
-    char* z = take(cv->grid_zero_bytes);
-    cv->grid.meta = (GridMeta*)z;
-    cv->grid.slab_cover = (uint32_t*)(z ? z + align_up(sizeof(GridMeta)) : nullptr);
-    cv->grid.slab_flag = (int*)(z ? z + align_up(sizeof(GridMeta)) + (size_t)kSlabCopies * kSlabWords * 4 : nullptr);
-    cv->grid.slab_tot = (int*)(z ? z + align_up(sizeof(GridMeta)) + align_up((size_t)kSlabCopies * kSlabWords * 4 + 64) : nullptr);
-    cv->grid.cnt = (int*)(z ? z + align_up(sizeof(GridMeta)) + slab_zero : nullptr);
-    cv->grid.start = (int*)take(((size_t)M + 4) * 4);
-    cv->grid.wsum = (int*)take((size_t)1024 * 4);
-    cv->grid.nparts = (int)((nn + 255) / 256);
-    cv->grid.bbpart = (int*)take((size_t)cv->grid.nparts * kBbInts * 4);
-    cv->grid.sorted = (float4*)take(nn * 16);
-    cv->grid.slot_of = (uint32_t*)take(nn * 4);
-    cv->grid.ulist = (uint32_t*)take(nn * 4);
+    cv.grid.mask = M - 1;
+    // GridMeta, the slab words and the slot counters are consecutive blocks: one contiguous range, zeroed before every build
+    const size_t zero_begin = w.total();
+    cv.grid.meta = w.take<GridMeta>(1);
+    cv.grid.slab_cover = w.take<uint32_t>((size_t)kSlabCopies * kSlabWords);
+    static_assert((size_t)kSlabCopies * kSlabWords * 4 % kWsAlign == 0, "slab_flag follows the cover words without a gap");
+    cv.grid.slab_flag = w.take<int>(16);
+    cv.grid.slab_tot = w.take<int>((size_t)(1 + kMaxTeams / 16) * kMaxSlabs);   // slab totals + group totals (slab_setup)
+    cv.grid_zero_bytes = w.total() - zero_begin + ((size_t)M + 4) * 4;
+    cv.grid.cnt = w.take<int>((size_t)M + 4);
+    cv.grid.start = w.take<int>((size_t)M + 4);
+    cv.grid.wsum = w.take<int>(1024);
+    cv.grid.nparts = (int)((nn + 255) / 256);
+    cv.grid.bbpart = w.take<int>((size_t)cv.grid.nparts * kBbInts);
+    cv.grid.sorted = w.take<float4>(nn);
+    cv.grid.slot_of = w.take<uint32_t>(nn);
+    cv.grid.ulist = w.take<uint32_t>(nn);
     const size_t n2 = nn + 64 * (size_t)kMaxSlabs;            // every slab starts on a 64-position boundary
-    cv->grid.slab_cnt = (int*)take((size_t)kMaxTeams * kMaxSlabs * 4);
-    cv->grid.slab_keep = (int*)take((size_t)kMaxSlabs * 4);
-    cv->grid.rec2 = (float4*)take(n2 * RotGeom::RECQ * 16);
-    cv->grid.order2 = (uint32_t*)take(n2 * 4);
-    cv->grid.pos_old = (uint32_t*)take(n2 * 4);
-    cv->grid.alive2_words = n2 / 64 + 10;
-    cv->grid.alive2 = (u64*)take(cv->grid.alive2_words * 8);
-    cv->grid.kept_words = nn / 64 + 2;
-    cv->grid.kept_bits = (u64*)take(cv->grid.kept_words * 8);
-    cv->grid.slab_plan = (SlabPlan*)take(sizeof(SlabPlan));
-    cv->mk_ctl = (int*)take(1024);
-    cv->mk_cidx = (uint32_t*)take((size_t)kMkCapMax * 4);
-    cv->mk_ent = (float4*)take((size_t)kMkCapMax * 16);
-    cv->mk_start = (uint16_t*)take((size_t)(kMkSlots + 8) * 2);
-    cv->mk_kbits = (u64*)take((size_t)(kMkCapMax / 64) * 8);
-    cv->mk_hasin = (uint8_t*)take((size_t)kMkCapMax);
-    cv->mk_pend1 = (uint4*)take((size_t)kMkPend1 * 16);
+    cv.grid.slab_cnt = w.take<int>((size_t)kMaxTeams * kMaxSlabs);
+    cv.grid.slab_keep = w.take<int>(kMaxSlabs);
+    cv.grid.rec2 = w.take<float4>(n2 * RotGeom::RECQ);
+    cv.grid.order2 = w.take<uint32_t>(n2);
+    cv.grid.pos_old = w.take<uint32_t>(n2);
+    cv.grid.alive2_words = n2 / 64 + 10;
+    cv.grid.alive2 = w.take<u64>(cv.grid.alive2_words);
+    cv.grid.kept_words = nn / 64 + 2;
+    cv.grid.kept_bits = w.take<u64>(cv.grid.kept_words);
+    cv.grid.slab_plan = w.take<SlabPlan>(1);
+    cv.mk_ctl = w.take<int>(256);
+    cv.mk_cidx = w.take<uint32_t>(kMkCapMax);
+    cv.mk_ent = w.take<float4>(kMkCapMax);
+    cv.mk_start = w.take<uint16_t>(kMkSlots + 8);
+    cv.mk_kbits = w.take<u64>(kMkCapMax / 64);
+    cv.mk_hasin = w.take<uint8_t>(kMkCapMax);
+    cv.mk_pend1 = w.take<uint4>(kMkPend1);
   }
-  cv->total = off;
-  return OBB_OK;
+  cv.total = w.total();
+  return cv;
+}
+
+// the fields of a launch that are the layout's own; the caller adds order, keep_out, max_keep, window, thr, thr64 and cull
+static void nms_args_from(const Carve& cv, int C, NmsArgs* a) {
+  a->rec = cv.rec; a->alive = cv.alive; a->seg_begin = cv.seg_begin; a->seg_end = cv.seg_end; a->keep_cnt = cv.keep_cnt;
+  a->rows = cv.rows; a->nrows = cv.nrows; a->edges = cv.edges; a->nedges = cv.nedges; a->ecap = cv.ecap; a->capmax = C;
 }
 
 // window of positions opened at a time when the caller limits the number of kept boxes (nms_core.h)
@@ -792,8 +787,7 @@ static int sort_single_list(const float* scores, int score_stride, const float* 
   const unsigned gb = (unsigned)((n + kPsRun - 1) / kPsRun);
   k_make_keys_wide<<<gb, kPsRun, 0, st>>>(scores, score_stride, dets5, drop_small, (int)n, cv.keys_a, cv.vals_a, x);
   *nparts_out = (int)gb;
-  uint32_t* hist = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(cv.sort_tmp) + align_up(ps_scratch_bytes()));
-  return seg_radix_sort_large(cv.keys_a, cv.keys_b, cv.vals_a, cv.vals_b, cv.seg_begin, cv.seg_end, 1, n, n, 0xF0u, hist, st);
+  return seg_radix_sort_large(cv.keys_a, cv.keys_b, cv.vals_a, cv.vals_b, cv.seg_begin, cv.seg_end, 1, n, n, 0xF0u, cv.sort_hist, st);
 }
 
 // kind: 0 rotated (5 floats + score array), 1 quad (rows of `stride` floats, score in column 8)
@@ -804,10 +798,8 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
   if (!num_keep || (n > 0 && (!boxes || !scores || !keep_out))) return OBB_ERR_BAD_ARG;
   const int C = cap_max(nseg);
   const int recq = kind == 0 ? RotGeom::RECQ : QuadGeom::RECQ;
-  Carve cv;
-  int rc = carve(ws, n, nseg, recq, C, &cv);
-  if (rc) return rc;
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  Carve cv = carve(ws, n, nseg, recq, C);
+  if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
   const int T = 256;
   const int drop_small = (flags & OBB_NMS_DROP_SMALL) ? 1 : 0;
   const unsigned gseg = 1;
@@ -836,8 +828,7 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
     x.mk16 = reinterpret_cast<uint4*>(cv.mk_ctl); x.n_mk16 = use_mk ? 64 : 0;
     x.bbpart = (use_grid && kind == 0) ? cv.grid.bbpart : nullptr;
     x.tstart = fbk ? cv.tstart : nullptr;
-    rc = sort_single_list(scores, score_stride, kind == 0 ? boxes : nullptr, kind == 0 ? drop_small : 0, n, cv, x, &cv.grid.nparts, st);
-    if (rc) return rc;
+    if (const int rc = sort_single_list(scores, score_stride, kind == 0 ? boxes : nullptr, kind == 0 ? drop_small : 0, n, cv, x, &cv.grid.nparts, st)) return rc;
     pre = kNmsBarZeroed;
   }
   {
@@ -903,10 +894,8 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
     const int slab_auto = (kept_before >= 0 && (int64_t)kept_before * 8 > n) ? 2048 : 1024;
     a.slab_cap = slab_auto;
   }
-  a.rec = cv.rec; a.order = cv.vals_b; a.alive = cv.alive; a.seg_begin = cv.seg_begin; a.seg_end = cv.seg_end;
-  a.keep_cnt = cv.keep_cnt; a.keep_out = keep_out;
-  a.rows = cv.rows; a.nrows = cv.nrows; a.edges = cv.edges; a.nedges = cv.nedges;
-  a.ecap = cv.ecap; a.n = (int)n; a.capmax = C;
+  nms_args_from(cv, C, &a);
+  a.order = cv.vals_b; a.keep_out = keep_out; a.n = (int)n;
   a.max_keep = (int)(max_keep > 0x7fffffffLL ? 0x7fffffffLL : (max_keep < 0 ? 0 : max_keep));
   a.window = nms_window(a.max_keep);
   a.thr = thr; a.thr64 = thr;
@@ -915,12 +904,10 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
   {
     ProfScope ps(PROF_NMS_STEPS, st);
     if (use_mk) {
-      rc = mk_steps(m, fbk ? *(volatile int*)(fbk->words + 1) : -1, st);
-      if (rc) return rc;
+      if (const int rc = mk_steps(m, fbk ? *(volatile int*)(fbk->words + 1) : -1, st)) return rc;
       a.resume = reinterpret_cast<const NmsResume*>(cv.mk_ctl);   // the persistent kernel behind them: returns at once when they completed the call
     }
-    rc = nms_steps(kind, a, cv, nseg, n, st, pre);
-    if (rc) return rc;
+    if (const int rc = nms_steps(kind, a, cv, nseg, n, st, pre)) return rc;
   }
   k_finalize<<<gseg, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, (int)nseg, max_keep, cv.abort_flag, num_keep, nullptr, fbk ? fbk->words : nullptr,
                                  a.slab_plan, use_mk ? 0 : 1, fbk ? cv.tstart : nullptr,
@@ -943,10 +930,8 @@ static int run_merge_nms(int kind, const double* dets9, int stride, int64_t n, c
   if (n > 0 && (!dets9 || !order || !keep_out)) return OBB_ERR_BAD_ARG;
   if (kind == 5 && stride < 4) return OBB_ERR_BAD_ARG;
   const int C = cap_max(nseg);
-  Carve cv;
-  int rc = carve(ws, n, nseg, kind_recq(kind), C, &cv);
-  if (rc) return rc;
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  const Carve cv = carve(ws, n, nseg, kind_recq(kind), C);
+  if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
   const int T = 256;
   const unsigned gseg = (unsigned)((nseg + T - 1) / T);
   k_seg_from_offsets<<<gseg, T, 0, st>>>(seg_off, (int)nseg, cv.seg_begin, cv.seg_end, cv.keep_cnt);
@@ -957,13 +942,10 @@ static int run_merge_nms(int kind, const double* dets9, int stride, int64_t n, c
   if (kind == 5) k_prep_hbb64<<<(unsigned)((n + T - 1) / T), T, 0, st>>>(dets9, stride, order, (int)n, (thr >= 0.0) ? 1 : 0, cv.rec, cv.alive);
   else k_prep_quad64<<<(unsigned)((n + T - 1) / T), T, 0, st>>>(dets9, order, (int)n, (thr >= 0.0) ? 1 : 0, cv.rec, cv.alive);
   NmsArgs a{};
-  a.rec = cv.rec; a.order = reinterpret_cast<const uint32_t*>(order); a.alive = cv.alive;
-  a.seg_begin = cv.seg_begin; a.seg_end = cv.seg_end; a.keep_cnt = cv.keep_cnt; a.keep_out = keep_out;
-  a.rows = cv.rows; a.nrows = cv.nrows; a.edges = cv.edges; a.nedges = cv.nedges;
-  a.ecap = cv.ecap; a.n = (int)n; a.capmax = C; a.max_keep = 0; a.window = 0;
+  nms_args_from(cv, C, &a);
+  a.order = reinterpret_cast<const uint32_t*>(order); a.keep_out = keep_out; a.n = (int)n; a.max_keep = 0; a.window = 0;
   a.thr = (float)thr; a.thr64 = thr; a.cull = 1;
-  rc = nms_steps(kind, a, cv, nseg, n, st);
-  if (rc) return rc;
+  if (const int rc = nms_steps(kind, a, cv, nseg, n, st)) return rc;
   k_finalize<<<gseg, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, (int)nseg, 0, cv.abort_flag, num_keep, nullptr);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
@@ -973,10 +955,8 @@ static int run_nms_rot64(const double* dets5, const double* scores, int64_t n, f
                          int64_t* num_keep, void* ws, size_t ws_bytes, hipStream_t st) {
   if (n < 0 || n > 0x7fffffffLL || !num_keep || (n > 0 && (!dets5 || !scores || !keep_out))) return OBB_ERR_BAD_ARG;
   const int C = cap_max(1);
-  Carve cv;
-  int rc = carve(ws, n, 1, RotGeom64::RECQ, C, &cv);
-  if (rc) return rc;
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  const Carve cv = carve(ws, n, 1, RotGeom64::RECQ, C);
+  if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
   const int T = 256;
   if (n == 0) {
     if (hipMemsetAsync(cv.keep_cnt, 0, 4, st) != hipSuccess || hipMemsetAsync(cv.seg_begin, 0, 4, st) != hipSuccess) return OBB_ERR_LAUNCH;
@@ -988,23 +968,16 @@ static int run_nms_rot64(const double* dets5, const double* scores, int64_t n, f
   k_make_keys_f64<<<gb, T, 0, st>>>(scores, dets5, drop_small, (int)n, cv.keys_a, cv.vals_a, cv.seg_begin, cv.seg_end, cv.keep_cnt);
   // 64-bit score keys are not unique: the stable LSD radix sort of segsort.h keeps ties in ascending index (eight passes; this
   // entry serves float64 callers, the double clip behind it costs orders of magnitude more than its sort)
-  {
-    uint32_t* hist = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(cv.sort_tmp) + align_up(ps_scratch_bytes()));
-    rc = seg_radix_sort_large(cv.keys_a, cv.keys_b, cv.vals_a, cv.vals_b, cv.seg_begin, cv.seg_end, 1, n, n, 0xFFu, hist, st);
-    if (rc) return rc;
-  }
+  if (const int rc = seg_radix_sort_large(cv.keys_a, cv.keys_b, cv.vals_a, cv.vals_b, cv.seg_begin, cv.seg_end, 1, n, n, 0xFFu, cv.sort_hist, st)) return rc;
   k_prep_rot64<<<gb, T, 0, st>>>(dets5, cv.vals_b, drop_small, (int)n, cv.rec, cv.alive);
   NmsArgs a{};
-  a.rec = cv.rec; a.order = cv.vals_b; a.alive = cv.alive; a.seg_begin = cv.seg_begin; a.seg_end = cv.seg_end;
-  a.keep_cnt = cv.keep_cnt; a.keep_out = keep_out;
-  a.rows = cv.rows; a.nrows = cv.nrows; a.edges = cv.edges; a.nedges = cv.nedges;
-  a.ecap = cv.ecap; a.n = (int)n; a.capmax = C;
+  nms_args_from(cv, C, &a);
+  a.order = cv.vals_b; a.keep_out = keep_out; a.n = (int)n;
   a.max_keep = (int)(max_keep > 0x7fffffffLL ? 0x7fffffffLL : (max_keep < 0 ? 0 : max_keep));
   a.window = nms_window(a.max_keep);
   a.thr = thr; a.thr64 = (double)thr;                      // the kernel's threshold is a float (nms_rotated_cuda.cu:14)
   a.cull = (thr >= 0.f) ? 1 : 0;
-  rc = nms_steps(3, a, cv, 1, n, st);
-  if (rc) return rc;
+  if (const int rc = nms_steps(3, a, cv, 1, n, st)) return rc;
   k_finalize<<<1, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, 1, max_keep, cv.abort_flag, num_keep, nullptr);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
@@ -1020,11 +993,8 @@ using namespace obb;
 extern "C" {
 
 size_t obb_nms_workspace_bytes(int64_t n, int64_t nseg, int kind) {
-  Carve cv;
-  if (n < 0 || nseg < 1) return 0;
-  if (kind < 0 || kind > 5) return 0;
-  if (carve(nullptr, n, nseg, kind_recq(kind), cap_max(nseg), &cv)) return 0;
-  return cv.total;
+  if (n < 0 || nseg < 1 || kind < 0 || kind > 5) return 0;
+  return carve(nullptr, n, nseg, kind_recq(kind), cap_max(nseg)).total;
 }
 
 int obb_nms_rotated_f32(const float* dets5, const float* scores, int64_t n, float iou_thr, int flags, int64_t max_keep,
@@ -1111,9 +1081,8 @@ void obb_cxx_poly_nms(int* keep_out_host, int* num_out_host, const float* polys_
 }
 
 size_t obb_nms_obb_workspace_bytes(int64_t bs, int64_t cap_img, int64_t nc, int agnostic) {
-  ObbCarve cv;
-  if (bs < 1 || cap_img < 1 || nc < 1 || nc > 256 || obb_carve(nullptr, bs, cap_img, agnostic ? 1 : nc, &cv)) return 0;
-  return cv.total;
+  if (bs < 1 || cap_img < 1 || nc < 1 || nc > 256) return 0;
+  return obb_carve(nullptr, bs, cap_img, agnostic ? 1 : nc).total;
 }
 
 int obb_non_max_suppression_obb(const void* pred, int dtype, int64_t bs, int64_t A, int64_t no, float conf_thres,

@@ -1355,33 +1355,29 @@ struct ObbCarve {
   int* seg_size;      // [bs][256] segment sizes for the planner of the in-LDS sort path
   int64_t* keep;
   Carve nms;          // rec/dead/segment state reuse the NMS carve (keys/vals/sort_tmp of it unused)
-  void* nms_base;
   size_t total;
 };
 
 static inline int64_t round_cap(int64_t cap_img) { return (cap_img + 63) / 64 * 64; }   // image regions start on alive-bitmap words
 
-static int obb_carve(void* base, int64_t bs, int64_t cap_img, int64_t ncs, ObbCarve* cv) {
+static ObbCarve obb_carve(void* base, int64_t bs, int64_t cap_img, int64_t ncs) {
   cap_img = round_cap(cap_img);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return base ? (char*)base + o : (char*)nullptr; };
+  ObbCarve cv{};
+  WsCursor w(base);
   const size_t n = (size_t)bs * cap_img;
-  cv->cand = (float4*)take(n * 32);
-  cv->keys_a = (unsigned long long*)take(n * 8); cv->keys_b = (unsigned long long*)take(n * 8);
-  cv->vals_a = (uint32_t*)take(n * 4); cv->vals_b = (uint32_t*)take(n * 4);
-  cv->cnt = (int*)take(bs * 4 * kCntPad); cv->sort_begin = (int*)take(bs * 4); cv->sort_end = (int*)take(bs * 4);
-  cv->img_end = (int*)take(bs * 4); cv->mode = (int*)take(bs * 4); cv->tiny = (int*)take(bs * 4);
-  cv->ticket = (int*)take(64 + (size_t)(bs + 1) * 4);         // 16 words + k_nms_small's output stage: [bs] + [1]
-  cv->seg_size = (int*)take((size_t)bs * 256 * 4);
-  cv->srs_hist = (uint32_t*)take((size_t)bs * ((size_t)(cap_img + kSrsTile - 1) / kSrsTile) * 256 * 4);
-  cv->keep = (int64_t*)take(n * 8);
+  cv.cand = w.take<float4>(n * 2);
+  cv.keys_a = w.take<unsigned long long>(n); cv.keys_b = w.take<unsigned long long>(n);
+  cv.vals_a = w.take<uint32_t>(n); cv.vals_b = w.take<uint32_t>(n);
+  cv.cnt = w.take<int>(bs * kCntPad); cv.sort_begin = w.take<int>(bs); cv.sort_end = w.take<int>(bs);
+  cv.img_end = w.take<int>(bs); cv.mode = w.take<int>(bs); cv.tiny = w.take<int>(bs);
+  cv.ticket = w.take<int>(16 + (size_t)(bs + 1));            // 16 words + k_nms_small's output stage: [bs] + [1]
+  cv.seg_size = w.take<int>((size_t)bs * 256);
+  cv.srs_hist = w.take<uint32_t>((size_t)bs * ((size_t)(cap_img + kSrsTile - 1) / kSrsTile) * 256);
+  cv.keep = w.take<int64_t>(n);
   // NMS state sized for bs * cap_img positions
-  cv->nms_base = base ? (char*)base + off : nullptr;
-  int rc = carve(cv->nms_base, (int64_t)n, bs * ncs, RotGeom::RECQ, cap_max(bs * ncs), &cv->nms);
-  if (rc) return rc;
-  off += cv->nms.total;
-  cv->total = off;
-  return OBB_OK;
+  w.nest([&](void* b) { return (cv.nms = carve(b, (int64_t)n, bs * ncs, RotGeom::RECQ, cap_max(bs * ncs))).total; });
+  cv.total = w.total();
+  return cv;
 }
 
 // The front kernel that reads the Detect head's conv outputs instead of `pred` (nms_head.h, obb_non_max_suppression_obb_head)
@@ -1409,14 +1405,13 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   // class segmentation needs the class in 8 and the anchor index in 24 key bits
   // (iou_thres < 0: IoU = 0 > thr, boxes of different classes DO suppress each other in the reference's single list)
   const int class_ok = (!agnostic && nc > 1 && A + n_extra < (1ll << 24) && iou_thres >= 0.f && max_wh > 0.f) ? 1 : 0;
-  ObbCarve cv;
-  int rc = obb_carve(ws, bs, cap_img, ncs, &cv);
-  if (rc) return rc;
-  if (!ws || ((uintptr_t)ws & 255u) || ws_bytes < cv.total) return OBB_ERR_WORKSPACE;
+  ObbCarve cv = obb_carve(ws, bs, cap_img, ncs);
+  if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
+  int rc = OBB_OK;
   // caller-kept counters: zero when the call starts (the caller's memset, or the previous call's last kernel) -- no reset launch
   const bool kept = state != nullptr;
   if (kept) {
-    if (state_bytes < obb_state_bytes(bs) || ((uintptr_t)state & 255u)) return OBB_ERR_WORKSPACE;
+    if (!ws_ok(state, state_bytes, obb_state_bytes(bs))) return OBB_ERR_WORKSPACE;
     cv.cnt = (int*)state;
     cv.tiny = cv.cnt + bs * kCntPad;
   }
@@ -1490,18 +1485,16 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   int *help_work = nullptr, *seg_np = nullptr, *seg_ticket = nullptr;
   u64 *part_main = nullptr, *part_help = nullptr;
   if (helpers > 0) {
-    const size_t nseg_b = align_up((size_t)(bs * ncs) * 4), work_b = align_up((size_t)helpers * 4);
-    const size_t main_b = align_up((size_t)bs * cap_img * kSmallWords * 8), help_b = align_up((size_t)helpers * kSmallMax * kSmallWords * 8);
+    auto lay = [&](void* base) {                                 // the helpers' blocks, inside the edge lists
+      WsCursor w(base);
+      help_work = w.take<int>((size_t)helpers);
+      seg_np = w.take<int>((size_t)(bs * ncs)); seg_ticket = w.take<int>((size_t)(bs * ncs));
+      part_main = w.take<u64>((size_t)bs * cap_img * kSmallWords);
+      part_help = w.take<u64>((size_t)helpers * kSmallMax * kSmallWords);
+      return w.total();
+    };
     const size_t have = (size_t)((bs * ncs < (int64_t)cu_count()) ? bs * ncs : (int64_t)cu_count()) * (size_t)nv.ecap * 4;   // (carve: nteams x ecap)
-    if (work_b + 2 * nseg_b + main_b + help_b > have) helpers = 0;
-    else {
-      char* p = reinterpret_cast<char*>(nv.edges);
-      help_work = (int*)p; p += work_b;
-      seg_np = (int*)p; p += nseg_b;
-      seg_ticket = (int*)p; p += nseg_b;
-      part_main = (u64*)p; p += main_b;
-      part_help = (u64*)p;
-    }
+    if (lay(nullptr) > have) helpers = 0; else lay(nv.edges);
   }
   // Self-sorting segments (SmallSelfSort): no sort launch when the small-segment kernel writes the rows itself and every segment is
   // one workgroup's.  OBB_NMS_SELF_SORT=0 keeps the sort kernel (read per call: tests compare the two in one process).
@@ -1570,10 +1563,8 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   }
 
   NmsArgs a{};
-  a.rec = nv.rec; a.order = nullptr; a.alive = nv.alive; a.seg_begin = nv.seg_begin; a.seg_end = nv.seg_end;   // keep_out: sorted positions
-  a.keep_cnt = nv.keep_cnt; a.keep_out = cv.keep;
-  a.rows = nv.rows; a.nrows = nv.nrows; a.edges = nv.edges; a.nedges = nv.nedges;
-  a.ecap = nv.ecap; a.n = (int)(bs * cap_img); a.capmax = cap_max(bs * ncs);
+  nms_args_from(nv, cap_max(bs * ncs), &a);
+  a.order = nullptr; a.keep_out = cv.keep; a.n = (int)(bs * cap_img);                  // keep_out: sorted positions
   a.max_keep = (int)max_det; a.window = nms_window(max_det); a.thr = iou_thres; a.cull = (iou_thres >= 0.f) ? 1 : 0;
   // the output stage runs inside k_nms_small unless the caller wants packed rows (SmallGather)
   const bool fused_out = small_nms && !out_packed;
