@@ -112,7 +112,10 @@ size_t obb_nms_workspace_bytes(int64_t n, int64_t nseg, int kind);
  * Lists of >= 16384 boxes without max_keep: two implementations of the same lazy chunked greedy NMS sit behind this entry -- a chain
  * of ordinary launches, one per phase (no co-residency needed), and one persistent kernel behind spin barriers (see
  * obb_nms_set_max_grid) -- and the library takes the one that was faster for the calling thread's previous calls of the size class
- * (four pinned words per size class that the device writes and the host reads without synchronising).  The persistent kernel is always
+ * (eight pinned words per size class that the device writes and the host reads, once per call, without synchronising: [0] the steps
+ * the call needed or -2 "started / handed over", [1] boxes kept, [2] slabs found, [3] steps enqueued -- written by the host --,
+ * [4] / [5] 10 ns ticks of the call on the persistent kernel / the phase kernels, [6] / [7] the kept counts those times came with;
+ * csrc/nms_plan.h names them).  The persistent kernel is always
  * launched last: it completes whatever the enqueued phases left undone and returns at once otherwise.
  */
 int obb_nms_rotated_f32(const float* dets5, const float* scores, int64_t n, float iou_thr, int flags, int64_t max_keep,

@@ -23,6 +23,7 @@
 #include "nms_small.h"
 #include "segsort.h"
 #include "ws_layout.h"
+#include "nms_plan.h"
 
 namespace obb {
 
@@ -396,11 +397,16 @@ __global__ void k_seg_from_offsets(const int32_t* __restrict__ seg_off, int nseg
 
 // num_keep[g] = -1 when the persistent kernel gave up on a barrier (abort flag): the host layer raises
 // feedback != NULL (a long single list of rotated boxes): what the calling thread's NEXT call of this size class chooses its path
-// by (mk_choose below) -- the number of kept boxes and whether the list fell apart into independent slabs.
+// by (nms_plan.h: mk_choose) -- the number of kept boxes and whether the list fell apart into independent slabs.
+struct FinalizeFeedback {          // default-constructed: none
+  int* feedback = nullptr; const SlabPlan* slab_plan = nullptr; int feedback_slab = 0; const u64* tstart = nullptr;
+  const NmsResume* mk_ctl = nullptr; int mk_enqueued = 0;
+};
 __global__ void k_finalize(const int* __restrict__ keep_cnt, const int* __restrict__ seg_begin, int nseg, long long max_keep,
                            const int* __restrict__ abort_flag, int64_t* __restrict__ num_keep, int64_t* __restrict__ seg_begin_out,
-                           int* feedback = nullptr, const SlabPlan* slab_plan = nullptr, int feedback_slab = 0, const u64* tstart = nullptr,
-                           const NmsResume* mk_ctl = nullptr, int mk_enqueued = 0) {
+                           FinalizeFeedback fb) {
+  int* const feedback = fb.feedback; const SlabPlan* const slab_plan = fb.slab_plan; const int feedback_slab = fb.feedback_slab;
+  const u64* const tstart = fb.tstart; const NmsResume* const mk_ctl = fb.mk_ctl; const int mk_enqueued = fb.mk_enqueued;
   int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= nseg) return;
   if (seg_begin_out) seg_begin_out[g] = seg_begin[g];
@@ -408,30 +414,25 @@ __global__ void k_finalize(const int* __restrict__ keep_cnt, const int* __restri
   if (max_keep > 0 && c > max_keep) c = max_keep;
   num_keep[g] = (abort_flag && *abort_flag) ? -1 : c;
   if (feedback != nullptr && g == 0) {
-    __hip_atomic_store(feedback + 1, (int)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(feedback + kFbKept, (int)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     // (only a call that looked for slabs reports on them: the phase-kernel path leaves the word alone)
-    if (feedback_slab) __hip_atomic_store(feedback + 2, (slab_plan != nullptr && slab_plan->mode == 1) ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    // how long the call took on the device (10 ns ticks from its first kernel to this one) and which path it was: [4 + path]
+    if (feedback_slab) __hip_atomic_store(feedback + kFbSlabs, (slab_plan != nullptr && slab_plan->mode == 1) ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // how long the call took on the device (10 ns ticks from its first kernel to this one) and which path it was
     // (a phase-kernel call that merely ran out of enqueued steps -- a stale step count from other data of this size class -- and was
     //  finished by the persistent kernel says nothing about the phase kernels' speed: its time is not recorded, the thread's next
     //  call enqueues twice the steps (hint -2) and reports then.  A call that bailed out, or had 32 steps, does report.)
     const bool starved = mk_ctl != nullptr && mk_ctl->done == 0 && mk_ctl->bail == 0 && mk_enqueued < 32;
     if (tstart != nullptr && !starved) {
       const u64 dtk = wall_clock64() - *tstart;
-      __hip_atomic_store(feedback + 4 + (feedback_slab ? 0 : 1), (int)(dtk > 0x3fffffffull ? 0x3fffffffull : dtk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(feedback + (feedback_slab ? kFbTicksPersist : kFbTicksMk), (int)(dtk > 0x3fffffffull ? 0x3fffffffull : dtk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       // ... and on how many kept boxes: a time measured on other data of the size class is not compared (mk_choose)
-      __hip_atomic_store(feedback + 6 + (feedback_slab ? 0 : 1), (int)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(feedback + (feedback_slab ? kFbKeptPersist : kFbKeptMk), (int)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
 }
 
 // ---------------------------------------------------------------- workspace (ws_layout.h)
-// Chunk capacities: the first chunk has 2048 boxes, later chunks double up to 8192 for a single list, 2048 per segment for
-// batches of up to 64 segments and 1024 beyond.  (The edge list of a team is sized for the worst case cap*(cap-1)/2 of one
-// chunk: 134 MB at 8192, 8.4 MB at 2048, 2 MB at 1024 -- times the number of teams.)
-constexpr int kCapFirst = 2048;     // clipped to cap_max in the kernel
-static int cap_max(int64_t nseg) { return nseg == 1 ? 8192 : (nseg <= 64 ? 2048 : 1024); }
-
+// (chunk capacities kCapFirst / cap_max: nms_limits.h)
 constexpr int kMaxTeams = 1024;     // >= number of CUs of any gfx950 part
 
 struct Carve {
@@ -456,14 +457,7 @@ struct Carve {
 // table slots of the spatial index (power of two, multiple of 4096)
 // cells of side 2 R_L / 2^fine (grid.h): 1 measured best at 100k (K=3000: 716 -> 648 us, uniform 2361 -> 2138; 2: no further gain)
 constexpr int kGridFine = 1;
-// Skip rules of the quad NMS (piou_device.h): bit 0 = the two exact cone rules (proved), bit 1 = the bounding-box rule (measured noise
-// bound).  OBB_NMS_POLY_STRICT=1: cone rule only (every other pair is clipped); =2: no rule at all, every pair is clipped.
-static int quad_skip() {
-  static const int f = [] { const char* e = getenv("OBB_NMS_POLY_STRICT"); const int v = e ? atoi(e) : 0; return v == 1 ? 1 : (v >= 2 ? 0 : 3); }();
-  return f;
-}
 static uint32_t grid_slots(int64_t n) { return n >= 32768 ? 65536u : 16384u; }
-constexpr int64_t kGridMinN = 8192;    // below this the exhaustive cross phase is cheaper than building the index
 
 // One persistent launch runs the whole step loop (nms_core.h).  Grid: one 512-thread workgroup per CU at most --
 // all workgroups must be resident because they meet at team barriers; smaller problems get fewer workgroups
@@ -555,14 +549,19 @@ static void nms_args_from(const Carve& cv, int C, NmsArgs* a) {
   a->rec = cv.rec; a->alive = cv.alive; a->seg_begin = cv.seg_begin; a->seg_end = cv.seg_end; a->keep_cnt = cv.keep_cnt;
   a->rows = cv.rows; a->nrows = cv.nrows; a->edges = cv.edges; a->nedges = cv.nedges; a->ecap = cv.ecap; a->capmax = C;
 }
-
-// window of positions opened at a time when the caller limits the number of kept boxes (nms_core.h)
-static int nms_window(long long max_keep) {
-  if (max_keep <= 0) return 0;
-  long long w = 4 * max_keep;
-  if (w < 8192) w = 8192;
-  if (w > (1 << 30)) w = 1 << 30;
-  return (int)((w + 63) / 64 * 64);
+// the caller's limit on the kept boxes (0: none) with its window, the threshold, and whether rejects may be culled: they predict
+// IoU <= 0 or IoU <= thr; with thr < 0 even IoU == 0 suppresses
+static void nms_args_limit(NmsArgs* a, int64_t max_keep, float thr) {
+  a->max_keep = (int)(max_keep > 0x7fffffffLL ? 0x7fffffffLL : (max_keep < 0 ? 0 : max_keep));
+  a->window = nms_window(a->max_keep);
+  a->thr = thr; a->cull = (thr >= 0.f) ? 1 : 0;
+}
+// a call without boxes: the counts of nseg empty segments (table: the segment table is written already)
+static int finalize_empty(const Carve& cv, int64_t nseg, bool table, long long max_keep, int64_t* num_keep, hipStream_t st) {
+  if (!table && (hipMemsetAsync(cv.keep_cnt, 0, nseg * 4, st) != hipSuccess || hipMemsetAsync(cv.seg_begin, 0, nseg * 4, st) != hipSuccess))
+    return OBB_ERR_LAUNCH;
+  k_finalize<<<(unsigned)((nseg + 255) / 256), 256, 0, st>>>(cv.keep_cnt, cv.seg_begin, (int)nseg, max_keep, nullptr, num_keep, nullptr, FinalizeFeedback{});
+  return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 
 constexpr size_t kPersistLdsMax = 159 * 1024;   // of the 160 KB per CU: exactly one workgroup per CU
@@ -595,23 +594,6 @@ static int launch_persist(const NmsArgs& a, unsigned nb, hipStream_t st) {   // 
   return OBB_OK;
 }
 
-// grid of the persistent launch.  n_slots: number of sorted positions that can hold a box (bounds the useful parallelism)
-static int nms_grid(int64_t nseg, int64_t n_slots, int cap_first_) {
-  const int cus = cu_count();
-  int64_t nb = (n_slots + 511) / 512;                 // 8 waves x 64 columns per workgroup
-  {                                                   // ... and one wave per tile of the first chunk's triangle
-    const int64_t per_seg = (n_slots + nseg - 1) / nseg;
-    const int64_t c = per_seg < cap_first_ ? per_seg : cap_first_;
-    const int64_t tiles = ((c + 63) / 64) * ((c + 63) / 64 + 1) / 2 * nseg;
-    if (nb < (tiles + 7) / 8) nb = (tiles + 7) / 8;
-  }
-  if (n_slots >= 8192) nb = cus;                      // enough work for the whole chip
-  if (nb < nseg) nb = nseg;
-  if (nb > cus) nb = cus;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
-
 constexpr int kNmsBarZeroed = 1;    // the caller has zeroed the barrier block on this stream already
 constexpr int kNmsPlanned = 2;      // the team plan for this launch has been written already (fused sort/prep kernel)
 static int nms_steps(int kind, NmsArgs& a, const Carve& cv, int64_t nseg, int64_t n_slots, hipStream_t st, int pre = 0) {
@@ -619,7 +601,7 @@ static int nms_steps(int kind, NmsArgs& a, const Carve& cv, int64_t nseg, int64_
   a.bar = cv.bar; a.abort_flag = cv.abort_flag; a.nseg = (int)nseg;
   a.bar_sub = cv.nedges + kMaxTeams;                 // group counters of the grid-wide barrier, behind the per-team words
   a.cap_first = kCapFirst;
-  static const int phase_prof = [] { const char* e = getenv("OBB_NMS_PHASE_PROF"); return (e && atoi(e)) ? 1 : 0; }();
+  static const int phase_prof = nms_env().phase_prof;   // (a once-per-process switch)
   a.prof = nullptr;
   if (phase_prof && a.resume == nullptr) {   // development aid: print the previous call's phase times (synchronises!)
     u64 h[56];
@@ -641,7 +623,7 @@ static int nms_steps(int kind, NmsArgs& a, const Carve& cv, int64_t nseg, int64_
     if (hipMemsetAsync(cv.prof, 0, 56 * 8, st) != hipSuccess) return OBB_ERR_LAUNCH;
     a.prof = cv.prof;
   }
-  const int nb = nms_grid(nseg, n_slots, a.cap_first);
+  const int nb = nms_grid(nseg, n_slots, a.cap_first, cu_count());
   a.plan = nullptr;
   if (nseg > 1) {                                      // workgroups in proportion to the (non-empty) segments' sizes
     int c1 = a.cap_first < a.capmax ? a.cap_first : a.capmax;
@@ -668,66 +650,23 @@ static int nms_steps(int kind, NmsArgs& a, const Carve& cv, int64_t nseg, int64_
 // returns at once when the control block says the call is complete, and whatever the enqueued steps leave undone is finished by
 // the persistent kernel launched behind them (NmsResume) -- which returns at once when nothing is left.  The device records the
 // number of steps a call needed in a pinned word of the calling thread (one per size class); the thread's next call of that size
-// enqueues that many.
-constexpr int64_t kMkMinN = 16384;
-constexpr int kMkMinKept = 256;    // below this many kept boxes (a handful of dense clusters: huge conflict lists per chunk) the phase kernels are not even tried
-static int mk_enabled() { const char* e = getenv("OBB_NMS_MK"); return e ? atoi(e) : 2; }   // 0: never, 1: always, 2: by feedback (read per call: tests switch paths in one process)
-// Per calling thread and size class (floor(log2 n)): four pinned words the DEVICE writes when a call completes -- [0] the steps
-// the phase-kernel path needed, [1] the boxes the call kept, [2] whether the persistent kernel found independent slabs -- and
-// the host reads, without synchronising, when the thread's next call of that size is set up.  Nothing but the choice of path and
-// the number of enqueued steps depends on them; the result of a call does not.
+// enqueues that many.  Which path a call takes, how many steps it enqueues and the feedback words' names: nms_plan.h.
 struct MkFeedback { int* words; unsigned calls; };
 static MkFeedback* mk_feedback(int64_t n) {
   static thread_local int* base = nullptr;
   static thread_local MkFeedback fb[64];
   if (!base) {
     void* p = nullptr;
-    if (hipHostMalloc(&p, 64 * 8 * sizeof(int), hipHostMallocPortable) != hipSuccess) return nullptr;
+    if (hipHostMalloc(&p, 64 * kFbWords * sizeof(int), hipHostMallocPortable) != hipSuccess) return nullptr;
     base = (int*)p;
-    for (int i = 0; i < 64 * 8; i++) base[i] = -1;
-    for (int i = 0; i < 64; i++) { fb[i].words = base + 8 * i; fb[i].calls = 0; }
+    for (int i = 0; i < 64 * kFbWords; i++) base[i] = -1;
+    for (int i = 0; i < 64; i++) { fb[i].words = base + kFbWords * i; fb[i].calls = 0; }
   }
   int b = 0;
   while ((n >> b) > 1 && b < 63) b++;
   return &fb[b];
 }
-// Which path the next call takes.  The phase kernels win where a chunk keeps many rows (thousands of objects, sparse data); the
-// persistent kernel wins where two or three steps with a few hundred kept rows each do it, and where the list falls apart into
-// independent slabs (class offsets: one team per slab steps concurrently).  Both report what the rule needs; the first call of a
-// size class, and every 64th after it, takes the persistent kernel (it is the one that can see slabs).
-// Round 6: the rule above only says where the phase kernels are WORTH TRYING.  Both paths report how long the call took on the device
-// ([4] persistent kernel, [5] phase kernels: 10 ns ticks between the call's first kernel and its k_finalize), and where both are
-// known the faster one is taken (S-clustered K=3000 + 18 class offsets keeps 40,000 boxes, finds no slabs -- and still runs 0.58 ms
-// on the persistent kernel against 0.67 ms here); the other one is measured again every 64th call, the data may have changed.
-static bool mk_choose(MkFeedback* f) {
-  const int mode = mk_enabled();
-  if (mode == 0) return false;
-  if (mode == 1 || f == nullptr) return mode == 1;
-  const unsigned k = f->calls++;
-  const int kept = *(volatile int*)(f->words + 1), slab = *(volatile int*)(f->words + 2);
-  if (kept < 0 || (k & 63u) == 0u) return false;
-  if (!(slab != 1 && kept >= kMkMinKept)) return false;
-  const int t_persist = *(volatile int*)(f->words + 4), t_mk = *(volatile int*)(f->words + 5);
-  // a time only counts for data like the data it was measured on: the kept count it came with ([6], [7]) within a quarter of the
-  // previous call's.  (bench.py switches regimes of one size class every 24 calls: K=3000 + 18 class offsets inherited "phase
-  // kernels are faster" from K=3000 and stayed on them at 0.62 ms against the persistent kernel's 0.51 until the 64th call.)
-  const int k_persist = *(volatile int*)(f->words + 6), k_mk = *(volatile int*)(f->words + 7);
-  auto stale = [&](int kk) { const int d = kk > kept ? kk - kept : kept - kk; return kk < 0 || d > kept / 4 + 16; };
-  if (t_mk <= 0 || stale(k_mk)) return true;           // (the phase kernels have not reported on such data yet: try them)
-  if (t_persist <= 0 || stale(k_persist)) return false;
-  if ((k & 63u) == 32u) return t_mk >= t_persist;      // the slower one's turn
-  return t_mk < t_persist;
-}
-// Which cross probe: the table of the kept rows in every workgroup's LDS (k_mk_cross_lds) where a step keeps a few thousand rows
-// at most -- the previous call of the size class kept <= 2 passes' worth in all -- the chunk's table in global memory otherwise
-// (S-uniform keeps 36,000 of 100,000: six passes over the queries would cost more than the L2 round trips they save).
-// OBB_NMS_MK_XLDS = 0 / 1 pins the choice (read per call: tests run both on the same data).
-static bool mk_cross_in_lds(int kept_prev) {
-  const char* e = getenv("OBB_NMS_MK_XLDS");
-  if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
-  return kept_prev >= 0 && kept_prev <= 2 * kMkXRows;
-}
-static int mk_steps(MkArgs& a, int kept_prev, hipStream_t st) {
+static int mk_steps(MkArgs& a, const SingleListPlan& plan, hipStream_t st) {
   static OncePerDevice attr;
   static_assert(sizeof(MkLdsSelect) <= kMkSerialLds && (size_t)RotGeom::SCR * 64 * 4 * kMkWaves <= kMkSerialLds, "serial-phase LDS");
   if (const int attr_dev = attr.need(); attr_dev != OncePerDevice::kDone) {
@@ -738,21 +677,10 @@ static int mk_steps(MkArgs& a, int kept_prev, hipStream_t st) {
       return OBB_ERR_LAUNCH;
     attr.mark(attr_dev);
   }
-  static const int fixed_steps = [] { const char* e = getenv("OBB_NMS_MK_STEPS"); return e ? atoi(e) : 0; }();   // (measurement aid)
-  // (-2: the previous call of this size class was finished by the persistent kernel behind its steps: twice as many this time)
-  int steps = 4;
-  if (a.hint_host) {
-    const int h = *(volatile int*)a.hint_host;
-    if (h >= 0) steps = h;
-    else if (h == -2) { const int last = *(volatile int*)(a.hint_host + 3); steps = last > 0 ? 2 * last : 8; }
-  }
-  if (fixed_steps > 0) steps = fixed_steps;
-  if (steps > 32) steps = 32;
-  if (steps < 1) steps = 1;
-  if (a.hint_host) { *(volatile int*)(a.hint_host + 3) = steps; }
+  const int steps = plan.steps;
+  if (a.hint_host) { *(volatile int*)(a.hint_host + kFbEnqueued) = steps; }
   const unsigned cus = (unsigned)hw_cu_count();
   const unsigned gp = 4 * cus;                         // (k_mk_probe: four 256-thread workgroups per CU)
-  const bool xlds = mk_cross_in_lds(kept_prev);
   k_mk_select<<<1, kMkThreads, kMkSerialLds, st>>>(a);
   for (int s = 0; s < steps; s++) {
     k_mk_probe<false><<<gp, kMkProbeThreads, 0, st>>>(a);
@@ -760,7 +688,7 @@ static int mk_steps(MkArgs& a, int kept_prev, hipStream_t st) {
     // (the step that completes a call has nothing behind its chunk: no cross half for the last enqueued step -- two empty launches,
     //  ~10 us; a call that needs more steps than were enqueued goes on in the persistent kernel with this cross phase, NmsResume stage 3)
     if (s == steps - 1) break;
-    if (xlds) k_mk_cross_lds<<<2 * cus, kMkXThreads, sizeof(MkLdsCross), st>>>(a);
+    if (plan.xlds) k_mk_cross_lds<<<2 * cus, kMkXThreads, sizeof(MkLdsCross), st>>>(a);
     else k_mk_probe<true><<<gp, kMkProbeThreads, 0, st>>>(a);
     k_mk_decide<true><<<cus, kMkThreads, kMkSerialLds, st>>>(a);       // ... + the next select in its last workgroup
   }
@@ -804,21 +732,19 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
   const int drop_small = (flags & OBB_NMS_DROP_SMALL) ? 1 : 0;
   const unsigned gseg = 1;
 
-  if (n == 0) {
-    if (hipMemsetAsync(cv.keep_cnt, 0, nseg * 4, st) != hipSuccess) return OBB_ERR_LAUNCH;
-    if (hipMemsetAsync(cv.seg_begin, 0, nseg * 4, st) != hipSuccess) return OBB_ERR_LAUNCH;
-    k_finalize<<<gseg, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, (int)nseg, max_keep, nullptr, num_keep, nullptr);
-    return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
-  }
+  if (n == 0) return finalize_empty(cv, nseg, false, max_keep, num_keep, st);
 
   const unsigned gb = (unsigned)((n + T - 1) / T);
   int pre = 0;
-  // spatial index for the cross phases (grid.h): rotated boxes, one list, conservative rejects allowed (thr >= 0)
-  const bool use_grid = kind == 0 && cv.grid.meta != nullptr && thr >= 0.f && n < (1ll << 24);
-  // long lists without a limit on the kept boxes: the phase-kernel path (nms_mk.h) -- no index of all boxes, no slab decomposition
-  MkFeedback* const fbk = (use_grid && cv.mk_cidx != nullptr && n >= kMkMinN && max_keep <= 0) ? mk_feedback(n) : nullptr;
-  const bool use_mk = use_grid && cv.mk_cidx != nullptr && n >= kMkMinN && max_keep <= 0 && mk_choose(fbk);
-  const bool use_slabs = use_grid && !use_mk && max_keep <= 0;   // (a limit on the kept boxes keeps the call one list: the windows are per list)
+  // the call's path (nms_plan.h), from ONE read of the thread's feedback words, before anything is enqueued
+  const NmsEnv env = nms_env();
+  const bool has_grid = cv.grid.meta != nullptr, has_mk = cv.mk_cidx != nullptr;
+  MkFeedback* const fbk = single_list_mk_possible(kind, n, thr, max_keep, has_grid, has_mk) ? mk_feedback(n) : nullptr;
+  FbSnapshot snap{};
+  if (fbk) snap = fb_snapshot(fbk->words);
+  const unsigned calls = mk_counts_call(env, fbk != nullptr) ? fbk->calls++ : 0u;
+  const SingleListPlan plan = plan_single_list(kind, n, thr, max_keep, has_grid, has_mk, fbk ? &snap : nullptr, calls, env);
+  const bool use_grid = plan.use_grid, use_mk = plan.use_mk, use_slabs = plan.use_slabs;
   {
     ProfScope ps(PROF_NMS_SORT, st);
     LocalExtras x{};
@@ -835,7 +761,7 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
     ProfScope ps(PROF_NMS_PREP, st);
     if (kind == 0) k_prep_rot<<<gb, T, 0, st>>>(boxes, cv.vals_b, drop_small, (int)n, cv.rec, cv.alive, cv.grid.bbpart, cv.grid.nparts,
                                                 use_slabs ? cv.grid.slab_cover : nullptr, cv.grid.slab_flag);
-    else k_prep_quad<<<gb, T, 0, st>>>(boxes, stride, cv.vals_b, (int)n, thr, quad_skip(), cv.rec, cv.alive);
+    else k_prep_quad<<<gb, T, 0, st>>>(boxes, stride, cv.vals_b, (int)n, thr, env.quad_skip, cv.rec, cv.alive);
   }
 
   MkArgs m{};
@@ -847,19 +773,12 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
     m.edges = cv.edges; m.nedges = cv.mk_ctl + 64; m.ecap = cv.ecap;
     m.rows = cv.rows; m.nrows = cv.mk_ctl + 128; m.keep_cnt = cv.keep_cnt; m.keep_out = keep_out;
     m.bbpart = cv.grid.bbpart; m.nparts = cv.grid.nparts;
-    // first chunk: 2048, or 4096 when the previous call of the size class kept more than an eighth of its boxes (sparse data: few
-    // conflicts inside a chunk, the steps are what costs -- measured at 100k: S-uniform 1.05 -> 0.94 ms, S-clustered K=3000 0.54 -> 0.58).
-    // (the edge list holds the worst case of kMkTile = C members; a larger chunk that outgrows it hands over to the persistent kernel)
-    const int kept_prev = fbk ? *(volatile int*)(fbk->words + 1) : -1;
-    m.capmax = kMkCapMax; m.cap_first = (kept_prev >= 0 && (int64_t)kept_prev * 8 > n) ? 4096 : 2048;
+    m.capmax = kMkCapMax; m.cap_first = plan.cap_first;
     static_assert(kMkTile == 8192, "cap_max(1)");
     m.thr = thr;
-    // (OBB_NMS_MK_PEND: a smaller pending list, so that tests reach the overflow hand-over without two million undecided pairs)
-    static const int mk_pend_cap = [] { const char* e = getenv("OBB_NMS_MK_PEND"); const int v = e ? atoi(e) : 0; return (v > 0 && v < kMkPend1) ? v : kMkPend1; }();
-    m.pend1 = cv.mk_pend1; m.cap1 = mk_pend_cap; m.num_keep = nullptr;    // (k_finalize below writes the count)
+    m.pend1 = cv.mk_pend1; m.cap1 = plan.pend_cap; m.num_keep = nullptr;    // (k_finalize below writes the count)
     m.hint_host = fbk ? fbk->words : nullptr;
-    static const int mk_prof = [] { const char* e = getenv("OBB_NMS_PHASE_PROF"); return (e && atoi(e)) ? 2 : 0; }();
-    if (mk_prof) {   // development aid: print the previous call's serial-phase times (synchronises!)
+    if (env.phase_prof) {   // development aid: print the previous call's serial-phase times (synchronises!)
       u64 h[56];
       if (hipMemcpy(h, cv.prof, sizeof h, hipMemcpyDeviceToHost) == hipSuccess && h[37] > 0 && h[37] < (1ull << 20)) {
         fprintf(stderr, "[mk phases, us, sums over %llu steps] pairs: decide+ticket %.1f (pending %llu) resolve %.1f [first round %.1f other rounds %.1f output %.1f; rounds %llu] | "
@@ -884,34 +803,26 @@ static int run_nms(int kind, const float* boxes, int stride, const float* scores
     a.rec2 = cv.grid.rec2; a.order2 = cv.grid.order2; a.pos_old = cv.grid.pos_old; a.alive2 = cv.grid.alive2; a.kept_bits = cv.grid.kept_bits;
     a.alive2_words = (int)cv.grid.alive2_words; a.kept_words = (int)cv.grid.kept_words;
     a.slab_plan = cv.grid.slab_plan;
-
-    // chunk capacity of a slab team: 1024 measured best at 100k / 18 slabs (512: 363 us, 1024: 330, 1536: 362, 1920: 383 --
-    // a team has ~14 workgroups: the pair phase grows with the square of the chunk, smaller chunks add steps)
-    // Round 6: twice that when the previous call of the size class kept more than an eighth of its boxes (thousands of objects per
-    // slab: few conflicts inside a chunk, the steps are what costs) -- S-clustered K=3000 + 18 class offsets (40,000 of 100,000 kept)
-    // 0.579 -> 0.506 ms, while K=300 + 18 offsets (6,900 kept) would lose 0.05 ms with it.
-    const int kept_before = fbk ? *(volatile int*)(fbk->words + 1) : -1;
-    const int slab_auto = (kept_before >= 0 && (int64_t)kept_before * 8 > n) ? 2048 : 1024;
-    a.slab_cap = slab_auto;
+    a.slab_cap = plan.slab_cap;
   }
   nms_args_from(cv, C, &a);
   a.order = cv.vals_b; a.keep_out = keep_out; a.n = (int)n;
-  a.max_keep = (int)(max_keep > 0x7fffffffLL ? 0x7fffffffLL : (max_keep < 0 ? 0 : max_keep));
-  a.window = nms_window(a.max_keep);
-  a.thr = thr; a.thr64 = thr;
-  a.cull = (thr >= 0.f) ? 1 : 0;      // rejects predict IoU <= 0 or IoU <= thr; with thr < 0 even IoU == 0 suppresses
+  nms_args_limit(&a, max_keep, thr);
+  a.thr64 = thr;
 
   {
     ProfScope ps(PROF_NMS_STEPS, st);
     if (use_mk) {
-      if (const int rc = mk_steps(m, fbk ? *(volatile int*)(fbk->words + 1) : -1, st)) return rc;
+      if (const int rc = mk_steps(m, plan, st)) return rc;
       a.resume = reinterpret_cast<const NmsResume*>(cv.mk_ctl);   // the persistent kernel behind them: returns at once when they completed the call
     }
     if (const int rc = nms_steps(kind, a, cv, nseg, n, st, pre)) return rc;
   }
-  k_finalize<<<gseg, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, (int)nseg, max_keep, cv.abort_flag, num_keep, nullptr, fbk ? fbk->words : nullptr,
-                                 a.slab_plan, use_mk ? 0 : 1, fbk ? cv.tstart : nullptr,
-                                 use_mk ? reinterpret_cast<const NmsResume*>(cv.mk_ctl) : nullptr, (use_mk && fbk) ? *(volatile int*)(fbk->words + 3) : 0);
+  FinalizeFeedback ff;
+  if (fbk) { ff.feedback = fbk->words; ff.tstart = cv.tstart; }
+  ff.slab_plan = a.slab_plan; ff.feedback_slab = use_mk ? 0 : 1;
+  if (use_mk) { ff.mk_ctl = reinterpret_cast<const NmsResume*>(cv.mk_ctl); ff.mk_enqueued = fbk ? plan.steps : 0; }
+  k_finalize<<<gseg, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, (int)nseg, max_keep, cv.abort_flag, num_keep, nullptr, ff);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 
@@ -935,18 +846,16 @@ static int run_merge_nms(int kind, const double* dets9, int stride, int64_t n, c
   const int T = 256;
   const unsigned gseg = (unsigned)((nseg + T - 1) / T);
   k_seg_from_offsets<<<gseg, T, 0, st>>>(seg_off, (int)nseg, cv.seg_begin, cv.seg_end, cv.keep_cnt);
-  if (n == 0) {
-    k_finalize<<<gseg, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, (int)nseg, 0, nullptr, num_keep, nullptr);
-    return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
-  }
+  if (n == 0) return finalize_empty(cv, nseg, true, 0, num_keep, st);
   if (kind == 5) k_prep_hbb64<<<(unsigned)((n + T - 1) / T), T, 0, st>>>(dets9, stride, order, (int)n, (thr >= 0.0) ? 1 : 0, cv.rec, cv.alive);
   else k_prep_quad64<<<(unsigned)((n + T - 1) / T), T, 0, st>>>(dets9, order, (int)n, (thr >= 0.0) ? 1 : 0, cv.rec, cv.alive);
   NmsArgs a{};
   nms_args_from(cv, C, &a);
-  a.order = reinterpret_cast<const uint32_t*>(order); a.keep_out = keep_out; a.n = (int)n; a.max_keep = 0; a.window = 0;
-  a.thr = (float)thr; a.thr64 = thr; a.cull = 1;
+  a.order = reinterpret_cast<const uint32_t*>(order); a.keep_out = keep_out; a.n = (int)n;
+  nms_args_limit(&a, 0, (float)thr);
+  a.thr64 = thr; a.cull = 1;                                 // (thr < 0: the records carry the rule, k_prep_*64)
   if (const int rc = nms_steps(kind, a, cv, nseg, n, st)) return rc;
-  k_finalize<<<gseg, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, (int)nseg, 0, cv.abort_flag, num_keep, nullptr);
+  k_finalize<<<gseg, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, (int)nseg, 0, cv.abort_flag, num_keep, nullptr, FinalizeFeedback{});
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 
@@ -958,11 +867,7 @@ static int run_nms_rot64(const double* dets5, const double* scores, int64_t n, f
   const Carve cv = carve(ws, n, 1, RotGeom64::RECQ, C);
   if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
   const int T = 256;
-  if (n == 0) {
-    if (hipMemsetAsync(cv.keep_cnt, 0, 4, st) != hipSuccess || hipMemsetAsync(cv.seg_begin, 0, 4, st) != hipSuccess) return OBB_ERR_LAUNCH;
-    k_finalize<<<1, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, 1, max_keep, nullptr, num_keep, nullptr);
-    return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
-  }
+  if (n == 0) return finalize_empty(cv, 1, false, max_keep, num_keep, st);
   const unsigned gb = (unsigned)((n + T - 1) / T);
   const int drop_small = (flags & OBB_NMS_DROP_SMALL) ? 1 : 0;
   k_make_keys_f64<<<gb, T, 0, st>>>(scores, dets5, drop_small, (int)n, cv.keys_a, cv.vals_a, cv.seg_begin, cv.seg_end, cv.keep_cnt);
@@ -973,12 +878,10 @@ static int run_nms_rot64(const double* dets5, const double* scores, int64_t n, f
   NmsArgs a{};
   nms_args_from(cv, C, &a);
   a.order = cv.vals_b; a.keep_out = keep_out; a.n = (int)n;
-  a.max_keep = (int)(max_keep > 0x7fffffffLL ? 0x7fffffffLL : (max_keep < 0 ? 0 : max_keep));
-  a.window = nms_window(a.max_keep);
-  a.thr = thr; a.thr64 = (double)thr;                      // the kernel's threshold is a float (nms_rotated_cuda.cu:14)
-  a.cull = (thr >= 0.f) ? 1 : 0;
+  nms_args_limit(&a, max_keep, thr);
+  a.thr64 = (double)thr;                                   // the kernel's threshold is a float (nms_rotated_cuda.cu:14)
   if (const int rc = nms_steps(3, a, cv, 1, n, st)) return rc;
-  k_finalize<<<1, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, 1, max_keep, cv.abort_flag, num_keep, nullptr);
+  k_finalize<<<1, T, 0, st>>>(cv.keep_cnt, cv.seg_begin, 1, max_keep, cv.abort_flag, num_keep, nullptr, FinalizeFeedback{});
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 

@@ -26,6 +26,7 @@
 #pragma once
 #include <cstddef>
 #include "nms_core.h"
+#include "nms_plan.h"
 
 namespace obb {
 
@@ -38,7 +39,6 @@ constexpr int kMkNE = 4;                  // entries a lane requests per trip of
 constexpr int kMkCapMax = 16384;          // largest chunk (chunk-local indices are 16-bit; the edge list holds the worst case of kMkTile members)
 constexpr int kMkTile = 8192;             // members a table build holds in registers at a time
 constexpr int kMkPer = kMkTile / kMkThreads;
-constexpr int kMkPend1 = 1 << 21;         // pending-list capacity (pairs); an overflow hands the call to the persistent kernel
 constexpr int kMkTabPad = kMkSlots / 32;  // LDS counters are padded one word per 32: a thread's 16 consecutive slots spread over the banks
 
 struct MkGrid {                           // geometry of a step's table (written by one workgroup, read by the probe kernels of later launches)
@@ -83,7 +83,7 @@ struct MkArgs {
   int capmax, cap_first;
   float thr;
   uint4* pend1; int cap1;                 // {query position, entry position, entry index << 16 | query index (pairs), -} the quick tests left undecided
-  int* hint_host;                         // pinned words: [0] steps the call needed, [1] boxes it kept (read by the NEXT call of this thread; may be NULL)
+  int* hint_host;                         // the pinned feedback words (nms_plan.h: FbWord; read by the NEXT call of this thread; may be NULL)
   u64* prof;                              // optional [56]: wall-clock ticks (10 ns) of the serial phases (OBB_NMS_PHASE_PROF=1; development aid)
 };
 
@@ -338,8 +338,8 @@ __device__ __forceinline__ void mk_finish(const MkArgs& a, MkCtl* c, int kept, i
   c->done = 1;
   if (a.num_keep) *a.num_keep = (int64_t)kept;
   if (a.hint_host) {
-    __hip_atomic_store(a.hint_host, steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(a.hint_host + 1, kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(a.hint_host + kFbSteps, steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(a.hint_host + kFbKept, kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -357,7 +357,7 @@ __device__ void mk_select_phase(const MkArgs& a, MkLdsSelect& S, u64* t0) {
     if (tid == 0) {
       c->dx0 = D.x0; c->dy0 = D.y0; c->dxr = D.xr; c->dyr = D.yr; c->drcap = D.rcap; c->dmag = D.mag; c->dmax2 = D.dmax2;
       // (the step count is not known before the call completes: -2 = "started", read by the thread's next call if nothing better follows)
-      if (a.hint_host) __hip_atomic_store(a.hint_host, -2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (a.hint_host) __hip_atomic_store(a.hint_host + kFbSteps, -2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
   const float dmax2 = D.dmax2;
@@ -654,7 +654,6 @@ __device__ void mk_probe_phase(const MkArgs& a, MkLdsProbe<NW>& S, int wg, int n
 // rules as mk_build_table / mk_probe_phase: brute rows in front, a query that is not well conditioned reads everything.
 constexpr int kMkXThreads = 512;
 constexpr int kMkXWaves = kMkXThreads / 64;
-constexpr int kMkXRows = 3072;            // kept rows of a pass
 constexpr int kMkXPer = kMkXRows / kMkXThreads;
 constexpr int kMkXSlots = 4096;           // 64 table rows of 64 cells
 constexpr int kMkXTabPad = kMkXSlots / 32;

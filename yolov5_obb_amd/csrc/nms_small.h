@@ -23,6 +23,7 @@
 // flag and is left alone: the host layer repeats the call on the persistent kernel (it chooses this kernel from the
 // previous call's largest segment, include/obb_hip.h: expected_cand).
 #pragma once
+#include "nms_limits.h"
 
 namespace obb {
 
@@ -33,8 +34,6 @@ __device__ unsigned long long g_small_trace_tail[2048 * 4];
 __device__ unsigned long long g_small_trace2[2048 * 8];
 #define STRACE(kind, ...) do { if (threadIdx.x == 0 && blockIdx.x < 2048) { const unsigned long long v_[] = {__VA_ARGS__}; unsigned long long* o_ = g_small_trace + blockIdx.x * 16; o_[0] = (kind); for (int z_ = 0; z_ < (int)(sizeof(v_) / 8) && z_ < 15; z_++) o_[1 + z_] = v_[z_]; } } while (0)
 #endif
-constexpr int kSmallMax = OBB_NMS_SMALL_SEG;        // boxes per segment (include/obb_hip.h)
-constexpr int kSmallWords = kSmallMax / 64;         // bit-matrix words per row
 constexpr int kSmallThreads = 512;
 constexpr int kSmallWaves = kSmallThreads / 64;
 
@@ -90,7 +89,6 @@ struct SmallFromSort { static constexpr bool kSelf = false; };   // FRONT of k_n
 // segment holds
 constexpr int kSmallClipWaves = 4;                 // the waves of a workgroup sit on four SIMDs: up to this many clip drains run side by side at full speed
 constexpr int kSmallSplit1 = 128;
-constexpr int kSmallHelpMax = 256;
 __host__ __device__ __forceinline__ int small_parts(int n) {
   return n <= kSmallSplit1 ? 1 : (n <= 192 ? 2 : (n <= 256 ? 4 : (n <= 320 ? 6 : 8)));
 }

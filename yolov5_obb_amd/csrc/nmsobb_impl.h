@@ -30,6 +30,7 @@
 #include "dtype_device.h"
 #include "obb_device.h"
 #include "segsort.h"
+#include "nms_plan.h"
 
 namespace obb {
 
@@ -150,7 +151,6 @@ constexpr int kCntPad = 64;   // ints
 // detector output is clustered (an object fires on neighbouring cells), so a few waves carried long serial chains of cold
 // row reads while most had none.  Now the workgroup compacts its passing rows into LDS and its four waves take them
 // round-robin, kDecDepth rows in flight per wave.
-constexpr int kDecThreads = 512;      // 8 waves: a workgroup whose share of rows is three times the median still needs one pass
 constexpr int kDecWaves = kDecThreads / 64;
 constexpr int kDecMaxG = 4;
 constexpr int kDecDepth = 2;          // groups of four rows in flight per wave
@@ -568,7 +568,6 @@ __global__ void k_pad_keys(unsigned long long* __restrict__ keys, uint32_t* __re
 // bitmap including its zero words (k_prep_cand + memset): six launches become one.  An image with more candidates than
 // the network takes is left empty; the caller sees its count in status[1] and calls again with that hint.
 constexpr int kSortLdsMax = OBB_NMS_SORT_LDS_MAX;
-constexpr int64_t kSortLdsHint = OBB_NMS_SORT_LDS_HINT;   // use the in-LDS path when the previous call's largest image was at most this
 __global__ __launch_bounds__(1024) void k_sort_prep_lds(const float4* __restrict__ cand, const unsigned long long* __restrict__ keys_in,
                                                         const uint32_t* __restrict__ vals_in, unsigned long long* __restrict__ keys_out,
                                                         uint32_t* __restrict__ vals_out, const int* __restrict__ cnt,
@@ -1395,18 +1394,17 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
     return OBB_ERR_BAD_ARG;
   if (A * nc + n_extra > 0xffffffffLL || bs * cap_img > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
   if (!dtype_known(dtype)) return OBB_ERR_BAD_ARG;
-  // expected_cand: low 32 bits = the previous call's largest candidate count of an image (0: unknown), high 32 bits = its
-  // largest NMS segment (0: unknown) -- both as status[1] reported them
-  const int64_t seg_hint = (expected_cand >> 32) & 0x1fffffff;
-  const bool small_hint = ((expected_cand >> 62) & 1) != 0;        // the previous call met short-sided boxes: run k_tiny_cross
-  expected_cand &= 0xffffffffll;
   cap_img = round_cap(cap_img);
-  const int ncs = agnostic ? 1 : nc;                               // NMS segments per image
-  // class segmentation needs the class in 8 and the anchor index in 24 key bits
-  // (iou_thres < 0: IoU = 0 > thr, boxes of different classes DO suppress each other in the reference's single list)
-  const int class_ok = (!agnostic && nc > 1 && A + n_extra < (1ll << 24) && iou_thres >= 0.f && max_wh > 0.f) ? 1 : 0;
-  ObbCarve cv = obb_carve(ws, bs, cap_img, ncs);
+  ObbCarve cv = obb_carve(ws, bs, cap_img, agnostic ? 1 : nc);
   if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
+  // the call's path (nms_plan.h): every choice below reads a field of the plan
+  ObbPlanIn pin{};
+  pin.bs = bs; pin.A = A; pin.nc = nc; pin.agnostic = agnostic; pin.multi_label = multi_label; pin.iou_thres = iou_thres; pin.max_wh = max_wh;
+  pin.n_extra = n_extra; pin.cap_img = cap_img; pin.max_nms = max_nms; pin.max_det = max_det; pin.expected_cand = expected_cand;
+  pin.out_packed = out_packed; pin.hw_cus = hw_cu_count(); pin.cus = cu_count(); pin.ecap = cv.nms.ecap;
+  pin.sort_tmp_bytes = cv.nms.sort_tmp_bytes; pin.ps_scratch_bytes = ps_scratch_bytes();
+  const ObbPlan plan = plan_nms_obb(pin, nms_env());
+  const int ncs = plan.ncs, class_ok = plan.class_ok, helpers = plan.helpers;
   int rc = OBB_OK;
   // caller-kept counters: zero when the call starts (the caller's memset, or the previous call's last kernel) -- no reset launch
   const bool kept = state != nullptr;
@@ -1418,7 +1416,7 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
 
   DecodeArgs d;
   d.pred = pred; d.objcol = objcol; d.A = A; d.no = (int)no; d.nc = nc; d.bs = (int)bs; d.conf_thres = conf_thres;
-  d.multi_label = (multi_label && nc > 1) ? 1 : 0;                 // :797
+  d.multi_label = plan.multi_label;
   d.cm.all = (classes_host == nullptr || n_classes <= 0) ? 1 : 0;
   for (int i = 0; i < 4; i++) d.cm.w[i] = 0ull;
   for (int i = 0; i < n_classes && classes_host; i++) {
@@ -1428,12 +1426,11 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   d.cap_img = cap_img; d.cand = cv.cand; d.keys = cv.keys_a; d.vals = cv.vals_a; d.cnt = cv.cnt; d.tiny = cv.tiny;
   d.win_lo = -0.35f * max_wh; d.win_hi = 0.6f * max_wh;            // 0.95 max_wh wide: circles of different classes cannot touch
 
-  const bool lds_sort = expected_cand > 0 && expected_cand <= kSortLdsHint;
   d.z_ticket = nullptr; d.n_ticket = 0; d.z_bar16 = nullptr; d.n_bar16 = 0; d.z_alive16 = nullptr; d.n_alive16 = 0;
   {
     Carve& nv0 = cv.nms;
     // (cap_img is a multiple of 64 -> bs * cap_img / 64 words; + the guard words, rounded up to 16 bytes)
-    const long long alive16 = lds_sort ? (long long)((((size_t)bs * cap_img) >> 6) + 8 + 1) / 2 : 0ll;
+    const long long alive16 = plan.lds_sort ? (long long)((((size_t)bs * cap_img) >> 6) + 8 + 1) / 2 : 0ll;
     if (kept) {                                                    // the filter kernel zeroes what the later launches need
       d.z_ticket = cv.ticket; d.n_ticket = (int)(16 + bs + 1);
       d.z_bar16 = reinterpret_cast<uint4*>(nv0.bar); d.n_bar16 = (long long)(nv0.bar_bytes / 16);
@@ -1444,8 +1441,7 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
                                          reinterpret_cast<uint4*>(nv0.alive), alive16);
     }
   }
-  // rows per workgroup: 2048 when that still gives two workgroups per CU, else 1024 / 512 (small batches, the TTA tensor)
-  d.rows_per_thread = (bs * A >= 4LL * kDecThreads * 480) ? 4 : (bs * A >= 2LL * kDecThreads * 480) ? 2 : 1;
+  d.rows_per_thread = plan.rows_per_thread;
   dim3 gd((unsigned)((A + kDecThreads * d.rows_per_thread - 1) / (kDecThreads * d.rows_per_thread)), (unsigned)bs);
   {
     ProfScope ps(PROF_DECODE, st);
@@ -1455,52 +1451,16 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
     } else OBB_DISPATCH_DTYPE(dtype, T, k_decode<T><<<gd, kDecThreads, 0, st>>>(d));
   }
   if (n_extra > 0 && extra8) k_append_extra<<<(unsigned)((n_extra + 255) / 256), 256, 0, st>>>(extra8, (int)n_extra, A, nc, d);
-  if (small_hint && class_ok)
+  if (plan.small_hint && class_ok)
     k_tiny_cross<<<dim3(kTinyParts, (unsigned)bs), 256, 0, st>>>(cv.cand, cv.keys_a, cv.cnt, cap_img, max_wh, iou_thres, cv.tiny);
   const unsigned gs = (unsigned)((bs + 255) / 256);
   Carve& nv = cv.nms;
-  const int64_t max_seg = (max_nms > 0 && max_nms < cap_img) ? max_nms : cap_img;
-  // grid of the NMS launch (needed by the planner inside the fused kernel)
-  const int nms_capmax = cap_max(bs * ncs);
-  const int plan_chunk = kCapFirst < nms_capmax ? kCapFirst : nms_capmax;
-  // Which NMS kernel: one workgroup per segment, everything in LDS (nms_small.h), when the previous call's largest segment fits it
-  // (class segments, the in-LDS sort, thr >= 0: its first decision stage uses the conservative bounds); else the persistent kernel.
-  const bool small_nms = lds_sort && class_ok && seg_hint > 0 && seg_hint <= kSmallMax && iou_thres >= 0.f && bs * ncs <= 65535;
-  const int plan_nb = (bs * ncs > 1 && !small_nms) ? nms_grid(bs * ncs, bs * max_seg, kCapFirst) : 0;
-  // k_nms_small's helper workgroups (nms_small.h: a large segment is shared by several workgroups).  A workgroup takes a whole CU
-  // (160 KB of LDS), so helpers only run at once with the segments' own workgroups on the CUs the segments leave free: as many as
-  // that, none for the bs16 x 16-class step whose 256 segments fill the device (measured there with 256 helpers: 0.121 -> 0.132 ms,
-  // the helpers start when the first small segments are through).  Their lists and the parts' bit matrices live in the persistent
-  // kernel's edge lists, which this path does not use.  OBB_NMS_SMALL_HELPERS = n pins the number (0: every segment stays whole).
-  const int helpers_env = [] { const char* e = getenv("OBB_NMS_SMALL_HELPERS"); const int v = (e && *e) ? atoi(e) : -1; return v > kSmallHelpMax ? kSmallHelpMax : v; }();   // (read per call: tests switch in one process)
-  // OBB_NMS_SELF_SORT (read per call): 0 = always the sort kernel, 1 = self-sorting segments where no helpers would run, 2 = default:
-  // self-sorting segments wherever they are possible (no helpers then: the sort kernel is what hands them out)
-  const int self_env = [] { const char* e = getenv("OBB_NMS_SELF_SORT"); return (e && *e >= '0' && *e <= '2') ? *e - '0' : 2; }();
-  const bool self_possible = small_nms && !out_packed && (int64_t)ncs * kSmallMax <= cap_img && self_env != 0;
-  int helpers = 0;
-  if (small_nms && !(self_possible && self_env == 2 && helpers_env < 0)) {
-    const int64_t free_cus = (int64_t)hw_cu_count() - bs * ncs;
-    helpers = helpers_env >= 0 ? helpers_env : (int)(free_cus < 0 ? 0 : (free_cus > kSmallHelpMax ? kSmallHelpMax : free_cus));
-  }
-  int *help_work = nullptr, *seg_np = nullptr, *seg_ticket = nullptr;
-  u64 *part_main = nullptr, *part_help = nullptr;
-  if (helpers > 0) {
-    auto lay = [&](void* base) {                                 // the helpers' blocks, inside the edge lists
-      WsCursor w(base);
-      help_work = w.take<int>((size_t)helpers);
-      seg_np = w.take<int>((size_t)(bs * ncs)); seg_ticket = w.take<int>((size_t)(bs * ncs));
-      part_main = w.take<u64>((size_t)bs * cap_img * kSmallWords);
-      part_help = w.take<u64>((size_t)helpers * kSmallMax * kSmallWords);
-      return w.total();
-    };
-    const size_t have = (size_t)((bs * ncs < (int64_t)cu_count()) ? bs * ncs : (int64_t)cu_count()) * (size_t)nv.ecap * 4;   // (carve: nteams x ecap)
-    if (lay(nullptr) > have) helpers = 0; else lay(nv.edges);
-  }
-  // Self-sorting segments (SmallSelfSort): no sort launch when the small-segment kernel writes the rows itself and every segment is
-  // one workgroup's.  OBB_NMS_SELF_SORT=0 keeps the sort kernel (read per call: tests compare the two in one process).
-  const bool self_sort = self_possible && helpers == 0;
-  if (self_sort) {
-  } else if (lds_sort) {
+  const int64_t max_seg = plan.max_seg;
+  // k_nms_small's helper blocks live in the persistent kernel's edge lists, which that path does not use (the plan has checked the fit)
+  SmallHelpBlocks hb{};
+  if (helpers > 0) { WsCursor w(nv.edges); hb = small_help_layout(w, helpers, bs * ncs, bs * cap_img); }
+  if (plan.self_sort) {                                           // no sort launch: k_nms_small orders its segments itself
+  } else if (plan.lds_sort) {
     ProfScope ps(PROF_SEGSORT, st);
     static OncePerDevice attr;
     const size_t lds = (size_t)kSortLdsMax * 12;
@@ -1509,13 +1469,12 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
         return OBB_ERR_LAUNCH;
       attr.mark(attr_dev);
     }
-    const int parts = (class_ok && ncs >= 8) ? 4 : 1;           // class-segment images: four workgroups each take every fourth class
-    k_sort_prep_lds<<<(unsigned)(bs * parts) + (plan_nb > 0 ? 1u : 0u), 1024, lds, st>>>(cv.cand, cv.keys_a, cv.vals_a, cv.keys_b, cv.vals_b, cv.cnt, cv.tiny, (int)bs, cap_img,
+    k_sort_prep_lds<<<(unsigned)(bs * plan.parts) + (plan.plan_nb > 0 ? 1u : 0u), 1024, lds, st>>>(cv.cand, cv.keys_a, cv.vals_a, cv.keys_b, cv.vals_b, cv.cnt, cv.tiny, (int)bs, cap_img,
                                                    max_nms, class_ok, A, nc, ncs, agnostic ? 0.f : max_wh, cv.sort_begin, cv.sort_end,
                                                    cv.img_end, cv.mode, nv.seg_begin, nv.seg_end, nv.keep_cnt,
-                                                   nv.rec, nv.alive, cv.ticket, plan_nb, plan_chunk, plan_nb > 0 ? nv.plan : nullptr,
-                                                   cv.seg_size, parts,
-                                                   helpers, help_work, seg_np, seg_ticket);
+                                                   nv.rec, nv.alive, cv.ticket, plan.plan_nb, plan.plan_chunk, plan.plan_nb > 0 ? nv.plan : nullptr,
+                                                   cv.seg_size, plan.parts,
+                                                   helpers, hb.work, hb.seg_np, hb.seg_ticket);
   } else {
    {
     ProfScope ps(PROF_SEGSORT, st);
@@ -1526,16 +1485,8 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
       k_rekey<<<gr, 256, 0, st>>>(cv.cand, cv.keys_a, cv.sort_begin, cv.sort_end, cv.mode, A, nc);
     }
     {
-      // Several images, or one: every image spread over many workgroups (segsort.h's LSD radix sort, two launches per key byte) --
-      // or, ONE large image (the TTA tensor) of up to kPsMaxN slots: the three-launch sort of psrs_sort.h over the image's
-      // candidates (keys are unique: the tie word; the count lives on the device).  This branch is what an un-hinted first call of a
-      // shape takes as well (the fused in-LDS path needs the previous call's largest candidate count).
-      int tb = 0;
-      while ((1ll << tb) < A * nc + n_extra + 1) tb++;                 // significant bits of the tie word
-      unsigned mask = 0xF0u;                                            // single-list key: score in bytes 4..7
-      for (int d = 0; d < 4; d++) if (tb > d * 8) mask |= 1u << d;
-      if (class_ok) mask = 0xFFu;                                       // + class-mode key: anchor 0..2, score 3..6, class 7
-      if (bs == 1 && cap_img <= kPsMaxN && nv.sort_tmp_bytes >= ps_scratch_bytes()) {
+      // the radix sort of segsort.h, or the three-launch sort of psrs_sort.h over ONE large image's candidates (nms_plan.h)
+      if (plan.psrs) {
         PsBuf b{};
         b.run_k = cv.keys_a; b.run_v = cv.vals_a; b.out_k = cv.keys_b; b.out_v = cv.vals_b;      // (the runs are sorted in place)
         b.n = (int)cap_img; b.n_dev = cv.sort_end; b.err = nullptr;
@@ -1546,7 +1497,7 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
         if (rc) return rc;
       } else {
         rc = seg_radix_sort_large(cv.keys_a, cv.keys_b, cv.vals_a, cv.vals_b, cv.sort_begin, cv.sort_end, (int)bs, cap_img, bs * cap_img,
-                                  mask, cv.srs_hist, st);
+                                  plan.radix_mask, cv.srs_hist, st);
         if (rc) return rc;
       }
     }
@@ -1565,10 +1516,8 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   NmsArgs a{};
   nms_args_from(nv, cap_max(bs * ncs), &a);
   a.order = nullptr; a.keep_out = cv.keep; a.n = (int)(bs * cap_img);                  // keep_out: sorted positions
-  a.max_keep = (int)max_det; a.window = nms_window(max_det); a.thr = iou_thres; a.cull = (iou_thres >= 0.f) ? 1 : 0;
-  // the output stage runs inside k_nms_small unless the caller wants packed rows (SmallGather)
-  const bool fused_out = small_nms && !out_packed;
-  if (small_nms) {
+  a.max_keep = (int)max_det; a.window = plan.window; a.thr = iou_thres; a.cull = (iou_thres >= 0.f) ? 1 : 0;
+  if (plan.small_nms) {
     ProfScope ps(PROF_STEPS, st);
     static OncePerDevice attr;
     const size_t lds = small_lds_bytes<RotGeom>();
@@ -1583,17 +1532,17 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
     sa.rec = nv.rec; sa.alive = nv.alive; sa.seg_begin = nv.seg_begin; sa.seg_end = nv.seg_end; sa.keep_cnt = nv.keep_cnt;
     sa.keep_out = cv.keep; sa.too_big = cv.ticket + 8; sa.thr = iou_thres; sa.max_keep = (int)max_det;
     sa.ncs = ncs; sa.mode = cv.mode;
-    sa.helpers = helpers; sa.help_cnt = cv.ticket + 12; sa.work = help_work; sa.seg_np = seg_np; sa.seg_ticket = seg_ticket;
-    sa.part_main = part_main; sa.part_help = part_help;
+    sa.helpers = helpers; sa.help_cnt = cv.ticket + 12; sa.work = hb.work; sa.seg_np = hb.seg_np; sa.seg_ticket = hb.seg_ticket;
+    sa.part_main = hb.part_main; sa.part_help = hb.part_help;
     const unsigned gsmall = (unsigned)(bs * ncs + helpers);      // (the helpers are the FIRST blocks: dispatched before the segments' own workgroups)
-    if (fused_out) {
+    if (plan.fused_out) {                                        // the output stage runs inside k_nms_small (SmallGather)
       // (keys_a / vals_a, the sort's input, are free: they take what the segments publish)
       sa.keys_sorted = cv.keys_b; sa.vals_sorted = cv.vals_b; sa.pub_key = cv.keys_a; sa.pub_val = cv.vals_a; sa.n_pos = bs * cap_img;
       SmallGather::Args ga{};
       ga.cand = cv.cand; ga.cnt = cv.cnt; ga.tiny = cv.tiny; ga.info = cv.ticket; ga.ticket = cv.ticket + 16;
       ga.out = out; ga.out_count = out_count; ga.status = status; ga.cap_img = cap_img; ga.max_det = max_det; ga.bs = (int)bs;
       ga.clean_cnt = kept ? cv.cnt : nullptr; ga.clean_tiny = kept ? cv.tiny : nullptr;
-      if (self_sort) {
+      if (plan.self_sort) {
         // (the segments read keys_a, the filter kernel's output, while others publish: keys_b / vals_b, the sort's output places, are free)
         sa.pub_key = cv.keys_b; sa.pub_val = cv.vals_b; sa.keys_sorted = nullptr; sa.vals_sorted = nullptr;
         sa.keys_in = cv.keys_a; sa.cand = cv.cand; sa.cnt = cv.cnt; sa.tiny = cv.tiny; sa.cap_img = cap_img; sa.max_nms = max_nms; sa.A = A; sa.nc = nc;
@@ -1606,14 +1555,12 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
     }
   } else {
     ProfScope ps(PROF_STEPS, st);
-    rc = nms_steps(0, a, nv, bs * ncs, bs * max_seg, st, kNmsBarZeroed | ((lds_sort && plan_nb > 0) ? kNmsPlanned : 0));
+    rc = nms_steps(0, a, nv, bs * ncs, bs * max_seg, st, kNmsBarZeroed | ((plan.lds_sort && plan.plan_nb > 0) ? kNmsPlanned : 0));
     if (rc) return rc;
   }
-  if (!fused_out) {
+  if (!plan.fused_out) {
     ProfScope ps(PROF_GATHER, st);
-    // parts per image: one up to ~2k expected candidates (the kept rows fit the kernel's LDS and 256 threads), then one per 1024
-    const unsigned gparts = expected_cand <= 2048 ? 1u : (unsigned)((expected_cand + 1023) / 1024 > 16 ? 16 : (expected_cand + 1023) / 1024);
-    k_gather_out<<<dim3((unsigned)bs, gparts), 256, 0, st>>>(cv.cand, cv.vals_b, cv.keys_b, cv.keep, nv.seg_begin, nv.keep_cnt, cv.mode, ncs, max_det,
+    k_gather_out<<<dim3((unsigned)bs, plan.gparts), 256, 0, st>>>(cv.cand, cv.vals_b, cv.keys_b, cv.keep, nv.seg_begin, nv.keep_cnt, cv.mode, ncs, max_det,
                                               out, out_count, cv.cnt, cap_img, status, nv.abort_flag, out_packed, cv.ticket, cv.tiny,
                                               kept ? cv.cnt : nullptr, kept ? cv.tiny : nullptr);
   }

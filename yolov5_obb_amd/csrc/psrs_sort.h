@@ -19,6 +19,7 @@
 // unique (score bits in the high word, original index / tie word in the low one), which IS the reference's documented
 // order here -- descending score, ties by ascending index.  Lists longer than kPsMaxN take segsort.h's LSD radix sort.
 #pragma once
+#include "nms_limits.h"
 
 namespace obb {
 
@@ -128,7 +129,7 @@ constexpr int kPsRun = 512;                         // elements per run = thread
 constexpr int kPsSamp = 16;                         // regular samples per run
 constexpr int kPsStride = kPsRun / kPsSamp;         // 32
 constexpr int kPsMaxRuns = 256;
-constexpr int kPsMaxN = kPsRun * kPsMaxRuns;        // 131072
+static_assert(kPsMaxN == kPsRun * kPsMaxRuns, "nms_limits.h");
 constexpr int kPsBucketCap = kPsRun + kPsMaxRuns * kPsStride;   // 8704: the regular-sampling bound (see above)
 constexpr int kPsSortMax = 2048;                    // buckets up to this size are sorted by the register / LDS network
 constexpr unsigned long long kPsPadHi = 0xFFFFFFFF00000000ull;   // pad key = kPsPadHi | position: above every real key, unique
