@@ -413,7 +413,8 @@ int obb_nms_obb_hints_update(obb_nms_obb_hints* hints_host, int64_t* cap_img_hos
  * CSL-angle losses, forward and backward, for raw head outputs p[i] of shape (bs, na, ny_i, nx_i, no) and the
  * dataloader's target tensor (nt, 7+180) rows [img, cls, cx, cy, l, s, theta, csl x 180] in pixels
  * (utils/datasets.py:637-672) -- or (nt, 7) rows without the labels, see obb_loss_config.csl_radius.  Everything ComputeLoss.__init__ reads from the model (utils/loss.py:93-120) travels
- * in obb_loss_config (host memory, plain C).
+ * in obb_loss_config (host memory, plain C).  obb_loss_config.head_layout = OBB_LOSS_LAYOUT_CONV hands over the 1x1 convs' own
+ * outputs (bs, na*no, ny_i, nx_i) instead of the permuted copies, and takes the gradient in that layout (same bits).
  */
 #define OBB_LOSS_MAX_LEVELS 8
 #define OBB_LOSS_MAX_ANCHORS 8
@@ -435,7 +436,19 @@ typedef struct obb_loss_config {
                                           (utils/rboxs_utils.py:9-26, utils/datasets.py:639-642) -- SURVEY 8(f) row 3   */
   float fl_gamma;                      /* hyp['fl_gamma']: > 0 wraps the class, angle and objectness BCE in FocalLoss(gamma,
                                           alpha = 0.25) like utils/loss.py:107-110 (35-62); 0: plain BCE                */
+  int32_t head_layout;                 /* OBB_LOSS_LAYOUT_*: where obb_loss_forward / _backward find element (b, a, gj, gi, ch) of
+                                          p_levels_host[i] and grad_levels_host[i].  A zero-initialised config is the row layout.
+                                          Any other value: obb_loss_workspace_bytes answers 0 and the four entries answer
+                                          OBB_ERR_BAD_ARG before any device call.  obb_loss_build_targets / _export_targets read
+                                          no head tensor: they only check the value.                                          */
 } obb_loss_config;
+/* (bs, na, ny_i, nx_i, no) contiguous: element at (((b*na + a)*ny_i + gj)*nx_i + gi)*no + ch -- the reference's permuted copy */
+#define OBB_LOSS_LAYOUT_ROWS 0
+/* (bs, na*no, ny_i, nx_i) contiguous, the 1x1 conv's own output and its gradient: element at
+ * ((b*na + a)*no + ch)*ny_i*nx_i + gj*nx_i + gi.  Nothing transposes the head or its gradient (Detect.lazy_train).  loss_out and
+ * every gradient element are bit for bit those of OBB_LOSS_LAYOUT_ROWS on the permuted copy of the same data: the kernels keep
+ * the row -> thread assignment, the partial sums and the per-cell entry order, only the address of (cell, ch) differs. */
+#define OBB_LOSS_LAYOUT_CONV 1
 
 size_t obb_loss_workspace_bytes(const obb_loss_config* cfg, int64_t nt);
 
@@ -463,12 +476,24 @@ int obb_loss_export_targets(const obb_loss_config* cfg, int64_t nt, int level, i
  * A NaN box logit of a matched cell reaches lbox and, through the cell's objectness target iou.detach().clamp(0) (torch's
  * clamp propagates NaN, argsort under sort_obj_iou ranks it last), lobj and the gradients of the cell's channels 0..4.
  * The workspace keeps the matched rows and (round 5) a dense copy of every anchor row's objectness logit for obb_loss_backward
- * (which then reads 4 contiguous bytes per row instead of one 128-byte line of each 800-byte row): pass the same buffer, untouched. */
+ * (which then reads 4 contiguous bytes per row instead of one 128-byte line of each 800-byte row): pass the same buffer, untouched.
+ * cfg->head_layout = OBB_LOSS_LAYOUT_CONV: p_levels_host[i] is the conv output (bs, na*no, ny_i, nx_i); the objectness logits of an
+ * anchor are then one contiguous plane, so no dense copy is kept and the workspace is smaller by that column.  In both layouts
+ * every p_levels_host[i] (and grad_levels_host[i] below) must be 16-byte aligned: the kernels use 16-byte accesses from the base. */
 int obb_loss_forward(const obb_loss_config* cfg, const void* const* p_levels_host, int dtype, const float* targets, int64_t nt,
                      int64_t tcols, float* loss_out, void* ws, size_t ws_bytes, void* stream);
 /* Gradient of loss_out[0] with respect to every p[i], times *grad_scale (device scalar: the incoming dL/dloss, e.g.
- * the GradScaler factor).  grad_levels_host: HOST array of nl device pointers, same shapes / dtype as p; every
- * element is written exactly once (no prior zero-fill needed). */
+ * the GradScaler factor).  grad_levels_host: HOST array of nl device pointers, same shapes / dtype / layout as p (16-byte
+ * aligned); every element is written (no prior zero-fill needed).  cfg, p, targets and ws as obb_loss_forward left them.
+ * OBB_LOSS_LAYOUT_CONV: the gradient is the conv output's, (bs, na*no, ny_i, nx_i) contiguous -- one linear stream of zeros with
+ * the objectness gradient in the planes of channel 4 (k_loss_bwd_dense_conv), then the rows of the matched cells, one strided
+ * store per channel.
+ * Kernel resources of the conv-layout instantiations (gfx950, -Rpass-analysis=kernel-resource-usage; VGPR for f32 / f16 / bf16;
+ * none uses scratch or spills; DESIGN.md 4.8 has the row layout's beside them):
+ *   k_loss_dense_fwd<T, 1>      VGPR 40 / 40 / 40     SGPR 72             LDS 32 B   scratch 0
+ *   k_loss_entries_fwd<T, 1>    VGPR 94 / 92 / 94     SGPR 103            LDS 0      scratch 0
+ *   k_loss_entries_bwd<T, 1>    VGPR 150 / 150 / 150  SGPR 104            LDS 0      scratch 0
+ *   k_loss_bwd_dense_conv<T>    VGPR 66 / 70 / 70     SGPR 82 / 98 / 98   LDS 0      scratch 0 */
 int obb_loss_backward(const obb_loss_config* cfg, const void* const* p_levels_host, int dtype, const float* targets, int64_t nt,
                       int64_t tcols, const float* grad_scale, void* const* grad_levels_host, void* ws, size_t ws_bytes,
                       void* stream);

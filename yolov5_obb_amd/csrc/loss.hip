@@ -20,6 +20,11 @@
 //                       stores (the reference writes the tensor >= 3 times).
 //   k_loss_entries_bwd  the owner wave of each matched cell sums the hand-written gradients of all entries of the
 //                       cell in ascending entry order (deterministic) and overwrites the cell's row.
+//
+// The head is read, and its gradient written, in one of two layouts (obb_loss_config.head_layout): the reference's permuted copy
+// (bs, na, ny, nx, no), or the 1x1 conv's own output (bs, na*no, ny, nx) -- then nothing transposes the head before the loss or
+// its gradient behind it.  The kernels that touch the head take the layout as a template parameter (CellAddr / obj_offset: only
+// the address of (cell, ch) differs, so the results are the same bits); the conv layout's dense backward is k_loss_bwd_dense_conv.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
@@ -98,6 +103,26 @@ __device__ __forceinline__ CslRow csl_row(const LossDev& d, const float* tr) {
 }
 
 __device__ __forceinline__ unsigned long long lanemask_lt_l() { return (1ull << (threadIdx.x & 63)) - 1ull; }
+
+// ------------------------------------------------------------------ head layouts (include/obb_hip.h: OBB_LOSS_LAYOUT_*)
+// Where the channels of one cell lie, as element offsets from the level's base pointer; cell = ((b*na + a)*ny + gj)*nx + gi and
+// plane = ny*nx.  Everything else in the kernels below (which thread reads which row, every sum, the per-cell entry order) is
+// the same for both layouts, so the results are the same bits.
+constexpr int kRows = OBB_LOSS_LAYOUT_ROWS, kConv = OBB_LOSS_LAYOUT_CONV;
+template <int LAY> struct CellAddr;
+template <> struct CellAddr<kRows> {            // (bs, na, ny, nx, no): a row of no consecutive elements
+  size_t base;
+  __device__ __forceinline__ CellAddr(unsigned cell, unsigned no, unsigned) : base((size_t)cell * no) {}
+  __device__ __forceinline__ size_t at(int ch) const { return base + (size_t)ch; }
+};
+template <> struct CellAddr<kConv> {            // (bs, na*no, ny, nx): one element in each of no consecutive planes
+  size_t base, plane;
+  __device__ __forceinline__ CellAddr(unsigned cell, unsigned no, unsigned pl) : plane(pl) {
+    const unsigned ba = cell / pl;
+    base = (size_t)ba * no * pl + (cell - ba * pl);
+  }
+  __device__ __forceinline__ size_t at(int ch) const { return base + (size_t)ch * plane; }
+};
 
 // ------------------------------------------------------------------ build_targets (utils/loss.py:194-275)
 struct BtCand {          // one (offset, anchor, target) candidate of a level
@@ -230,7 +255,15 @@ __device__ __forceinline__ float wave_sum_f(float v) {
 }
 
 // ------------------------------------------------------------------ dense objectness pass (utils/loss.py:178-179, tobj = 0)
-template <typename T>
+// offset of the objectness logit of anchor row r (rows <= 2^30, loss_check).  kConv: consecutive rows of one (image, anchor) are
+// consecutive elements of its channel-4 plane, so a wave reads one or two lines where the row layout touches 64
+template <int LAY>
+__device__ __forceinline__ size_t obj_offset(long long r, int no, unsigned plane) {
+  if constexpr (LAY == kRows) return (size_t)r * no + 4;
+  else { const unsigned ba = (unsigned)r / plane; return ((size_t)ba * no + 4) * plane + ((unsigned)r - ba * plane); }
+}
+
+template <typename T, int LAY>
 __global__ __launch_bounds__(256) void k_loss_dense_fwd(const LossDev* __restrict__ dp) {
   __shared__ double s_part[4];
   const LossDev& d = *dp;
@@ -238,20 +271,26 @@ __global__ __launch_bounds__(256) void k_loss_dense_fwd(const LossDev* __restric
   const long long rows = d.rows[lv];
   const T* p = (const T*)d.p[lv];
   const int no = d.no;
+  const unsigned plane = (unsigned)d.ny[lv] * (unsigned)d.nx[lv];
   const float pw = d.obj_pw, fg = d.fl_gamma;
-  float* col = d.objcol + d.cell_off[lv];              // the level's slice of the dense logit column (the backward's input)
+  // the level's slice of the dense logit column (the row-layout backward's input; the conv layout keeps none: its planes are dense)
+  float* col = LAY == kRows ? d.objcol + d.cell_off[lv] : nullptr;
   float acc = 0.f;
   const long long step = (long long)gridDim.x * 256;
   long long r = (long long)blockIdx.x * 256 + tid;
   for (; r + 3 * step < rows; r += 4 * step) {       // 4 independent strided loads in flight
-    const float x0 = ld_as_float<T>(p + (size_t)r * no + 4);
-    const float x1 = ld_as_float<T>(p + (size_t)(r + step) * no + 4);
-    const float x2 = ld_as_float<T>(p + (size_t)(r + 2 * step) * no + 4);
-    const float x3 = ld_as_float<T>(p + (size_t)(r + 3 * step) * no + 4);
-    col[r] = x0; col[r + step] = x1; col[r + 2 * step] = x2; col[r + 3 * step] = x3;
+    const float x0 = ld_as_float<T>(p + obj_offset<LAY>(r, no, plane));
+    const float x1 = ld_as_float<T>(p + obj_offset<LAY>(r + step, no, plane));
+    const float x2 = ld_as_float<T>(p + obj_offset<LAY>(r + 2 * step, no, plane));
+    const float x3 = ld_as_float<T>(p + obj_offset<LAY>(r + 3 * step, no, plane));
+    if constexpr (LAY == kRows) { col[r] = x0; col[r + step] = x1; col[r + 2 * step] = x2; col[r + 3 * step] = x3; }
     acc += bce_focal(x0, 0.f, pw, fg); acc += bce_focal(x1, 0.f, pw, fg); acc += bce_focal(x2, 0.f, pw, fg); acc += bce_focal(x3, 0.f, pw, fg);
   }
-  for (; r < rows; r += step) { const float x = ld_as_float<T>(p + (size_t)r * no + 4); col[r] = x; acc += bce_focal(x, 0.f, pw, fg); }
+  for (; r < rows; r += step) {
+    const float x = ld_as_float<T>(p + obj_offset<LAY>(r, no, plane));
+    if constexpr (LAY == kRows) col[r] = x;
+    acc += bce_focal(x, 0.f, pw, fg);
+  }
   const double w = wave_sum_d((double)acc);
   if ((tid & 63) == 0) s_part[tid >> 6] = w;
   __syncthreads();
@@ -262,13 +301,13 @@ __global__ __launch_bounds__(256) void k_loss_dense_fwd(const LossDev* __restric
 template <typename T>
 struct RowRegs { float x[kChunks]; };
 
-template <typename T>
-__device__ __forceinline__ RowRegs<T> load_row(const T* row, int no, int lane) {
+template <typename T, int LAY>
+__device__ __forceinline__ RowRegs<T> load_row(const T* p, const CellAddr<LAY>& cell, int no, int lane) {
   RowRegs<T> r;
 #pragma unroll
   for (int k = 0; k < kChunks; k++) {
     const int ch = lane + 64 * k;
-    r.x[k] = (ch < no) ? ld_as_float<T>(row + ch) : 0.f;
+    r.x[k] = (ch < no) ? ld_as_float<T>(p + cell.at(ch)) : 0.f;
   }
   return r;
 }
@@ -280,7 +319,7 @@ __device__ __forceinline__ float clamp0_nan(float v) { return v < 0.f ? 0.f : v;
 __device__ __forceinline__ bool score_gt(float a, float b) { return (a != a) ? (b == b) : a > b; }
 __device__ __forceinline__ bool score_eq(float a, float b) { return a == b || (a != a && b != b); }
 
-template <typename T>
+template <typename T, int LAY>
 __global__ __launch_bounds__(256) void k_loss_entries_fwd(const LossDev* __restrict__ dp) {
   const LossDev& d = *dp;
   const int lane = threadIdx.x & 63;
@@ -291,8 +330,8 @@ __global__ __launch_bounds__(256) void k_loss_entries_fwd(const LossDev* __restr
     const int lv = eg / d.cap, pos = eg - lv * d.cap;
     if (pos >= d.counts[lv]) continue;
     const int cell = d.e_cell[eg], t = d.e_t[eg], a = d.e_ao[eg] & 255;
-    const T* row = (const T*)d.p[lv] + (size_t)cell * no;
-    const RowRegs<T> R = load_row<T>(row, no, lane);
+    const CellAddr<LAY> addr((unsigned)cell, (unsigned)no, (unsigned)d.ny[lv] * (unsigned)d.nx[lv]);
+    const RowRegs<T> R = load_row<T, LAY>((const T*)d.p[lv], addr, no, lane);
     const float l0 = __shfl(R.x[0], 0), l1 = __shfl(R.x[0], 1), l2 = __shfl(R.x[0], 2), l3 = __shfl(R.x[0], 3);
     const float x4 = __shfl(R.x[0], 4);
     const PredBox pb = loss_pred_box(l0, l1, l2, l3, d.anchors[lv][a][0], d.anchors[lv][a][1]);    // :148-149
@@ -467,7 +506,78 @@ __global__ __launch_bounds__(256) void k_loss_bwd_dense(const LossDev* __restric
   }
 }
 
+// The same for OBB_LOSS_LAYOUT_CONV.  A level's gradient is ONE linear buffer of rows*no elements, plane after plane (plane index
+// (b*na + a)*no + ch, ny*nx elements each): zero everywhere except in the planes of channel 4, where element i takes
+// d lobj / d p[i] -- p has the same layout, so the logit is p[i] itself, read contiguously from the plane (no objcol).
+// A wave takes chunks of 64*U consecutive 16-byte vectors.  The chunk's (plane, offset) costs one division per chunk (32-bit while
+// the index fits); a lane then steps over at most one plane boundary when planes are at least a chunk long, and divides otherwise
+// (small grids).  A vector inside one plane of another channel is a zero store.  One that touches a channel-4 plane, straddles a
+// plane boundary (ny*nx not a multiple of V, or a plane shorter than V) or the level's end is assembled element by element, every
+// load and store behind `i < total`.
 template <typename T>
+__global__ __launch_bounds__(256) void k_loss_bwd_dense_conv(const LossDev* __restrict__ dp) {
+  constexpr int V = Vec16<T>::V;
+  constexpr int U = 2;
+  constexpr unsigned kChunk = 64u * U * V;            // elements per wave chunk (512 fp32, 1024 fp16 / bf16)
+  const LossDev& d = *dp;
+  const int lv = blockIdx.y, lane = threadIdx.x & 63;
+  const long long rows = d.rows[lv];
+  const unsigned no = (unsigned)d.no, plane = (unsigned)d.ny[lv] * (unsigned)d.nx[lv];
+  const long long total = rows * no;
+  const T* p = (const T*)d.p[lv];
+  T* g = (T*)d.grad[lv];
+  const float pw = d.obj_pw, fg = d.fl_gamma;
+  const float gin = d.counts[kLv] ? __builtin_nanf("") : d.gscale[0];                   // (bad target rows: NaN, see k_loss_bwd_dense)
+  const float gs = gin * d.g_obj * (float)d.bs * d.balance[lv] / (float)rows;
+  const long long nchunk = (total + kChunk - 1) / kChunk;
+  for (long long c = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); c < nchunk; c += (long long)gridDim.x * 4) {
+    const long long e0 = c * kChunk;
+    unsigned s0, ch0;                                  // offset inside its plane and channel of element e0
+    if (e0 <= 0xffffffffLL) { const unsigned e = (unsigned)e0, q = e / plane; s0 = e - q * plane; ch0 = q % no; }
+    else { const long long q = e0 / plane; s0 = (unsigned)(e0 - q * plane); ch0 = (unsigned)(q % no); }
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+      const unsigned eo = (unsigned)(k * 64 + lane) * V;
+      const long long i0 = e0 + eo;
+      if (i0 >= total) continue;
+      unsigned s = s0 + eo, ch = ch0;                  // (s0 < plane <= 2^30, eo < kChunk: no overflow)
+      if (s >= plane) {
+        if (plane >= kChunk) { s -= plane; if (++ch == no) ch = 0; }
+        else { const unsigned dq = s / plane; s -= dq * plane; ch = (ch + dq) % no; }
+      }
+      const bool full = i0 + V <= total;
+      loss_u32x4* dst = reinterpret_cast<loss_u32x4*>(g + i0);                          // 16-byte aligned: i0 is a multiple of V
+      if (full && s + V <= plane && ch != 4) {
+        __builtin_nontemporal_store(loss_u32x4{0u, 0u, 0u, 0u}, dst);
+        continue;
+      }
+      float vals[V];
+#pragma unroll
+      for (int j = 0; j < V; j++) {
+        vals[j] = 0.f;
+        if (ch == 4 && i0 + j < total) vals[j] = bce_focal_grad(ld_as_float<T>(p + i0 + j), 0.f, pw, fg) * gs;
+        if (++s == plane) { s = 0; if (++ch == no) ch = 0; }
+      }
+      if (full) {
+        loss_u32x4 w;
+        if constexpr (V == 4) {
+          w = loss_u32x4{__float_as_uint(vals[0]), __float_as_uint(vals[1]), __float_as_uint(vals[2]), __float_as_uint(vals[3])};
+        } else {
+          w = loss_u32x4{bits16_from_float<T>(vals[0]) | (bits16_from_float<T>(vals[1]) << 16),
+                         bits16_from_float<T>(vals[2]) | (bits16_from_float<T>(vals[3]) << 16),
+                         bits16_from_float<T>(vals[4]) | (bits16_from_float<T>(vals[5]) << 16),
+                         bits16_from_float<T>(vals[6]) | (bits16_from_float<T>(vals[7]) << 16)};
+        }
+        __builtin_nontemporal_store(w, dst);
+      } else {
+#pragma unroll
+        for (int j = 0; j < V; j++) if (i0 + j < total) st_from_float<T>(g + i0 + j, vals[j]);
+      }
+    }
+  }
+}
+
+template <typename T, int LAY>
 __global__ __launch_bounds__(256) void k_loss_entries_bwd(const LossDev* __restrict__ dp) {
   const LossDev& d = *dp;
   const int lane = threadIdx.x & 63;
@@ -482,8 +592,8 @@ __global__ __launch_bounds__(256) void k_loss_entries_bwd(const LossDev* __restr
     const int cell = d.e_cell[eg];
     if (d.head[d.cell_off[lv] + cell] != eg + 1) continue;     // only the owner of the cell writes its row
     const int a = d.e_ao[eg] & 255;
-    const T* row = (const T*)d.p[lv] + (size_t)cell * no;
-    const RowRegs<T> R = load_row<T>(row, no, lane);
+    const CellAddr<LAY> addr((unsigned)cell, (unsigned)no, (unsigned)d.ny[lv] * (unsigned)d.nx[lv]);
+    const RowRegs<T> R = load_row<T, LAY>((const T*)d.p[lv], addr, no, lane);
     const float l0 = __shfl(R.x[0], 0), l1 = __shfl(R.x[0], 1), l2 = __shfl(R.x[0], 2), l3 = __shfl(R.x[0], 3);
     const float x4 = __shfl(R.x[0], 4);
     const PredBox pb = loss_pred_box(l0, l1, l2, l3, d.anchors[lv][a][0], d.anchors[lv][a][1]);
@@ -522,11 +632,11 @@ __global__ __launch_bounds__(256) void k_loss_entries_bwd(const LossDev* __restr
     (void)w;
     const float tobj = round_to_dtype<T>((1.0f - d.gr) + d.gr * round_to_dtype<T>(clamp0_nan(iou_w)));
     const float g4 = bce_focal_grad(x4, tobj, d.obj_pw, d.fl_gamma) * s_obj;
-    T* grow = (T*)d.grad[lv] + (size_t)cell * no;
+    T* g = (T*)d.grad[lv];                          // (kConv: one store per channel plane)
 #pragma unroll
     for (int k = 0; k < kChunks; k++) {
       const int ch = lane + 64 * k;
-      if (ch < no) st_from_float<T>(grow + ch, (ch == 4) ? g4 : acc[k]);
+      if (ch < no) st_from_float<T>(g + addr.at(ch), (ch == 4) ? g4 : acc[k]);
     }
   }
 }
@@ -543,6 +653,7 @@ struct LossCarve {
 static int loss_check(const obb_loss_config* c, int64_t nt) {
   if (!c || c->nl < 1 || c->nl > kLv || c->na < 1 || c->na > kNa || c->nc < 1 || c->nc > 256 || c->bs < 1 || nt < 0) return OBB_ERR_BAD_ARG;
   if (c->no != 5 + c->nc + kCslBins) return OBB_ERR_BAD_ARG;
+  if (c->head_layout != kRows && c->head_layout != kConv) return OBB_ERR_BAD_ARG;
   long long tot = 0;
   for (int i = 0; i < c->nl; i++) {
     if (c->ny[i] < 1 || c->nx[i] < 1) return OBB_ERR_BAD_ARG;
@@ -568,7 +679,7 @@ static LossCarve loss_carve(void* base, const obb_loss_config* c, int64_t nt) {
   cv.e_tbox = w.take<float4>(ce);
   cv.part_box = w.take<float>(ce); cv.part_cls = w.take<float>(ce); cv.part_th = w.take<float>(ce); cv.part_obj = w.take<float>(ce);
   cv.dense_part = w.take<double>((size_t)kLv * kDenseBlocks);
-  cv.objcol = w.take<float>((size_t)tot);
+  cv.objcol = c->head_layout == kRows ? w.take<float>((size_t)tot) : nullptr;      // (the conv layout reads the logits from their planes)
   cv.lvl_out = w.take<float>(kLv * 4);
   cv.blkcnt = w.take<int>(((size_t)5 * c->na * (size_t)nt / 1024 + 2) * c->nl);
   cv.total = w.total();
@@ -622,6 +733,11 @@ static unsigned entry_grid(const LossDev& d) {
 
 using namespace obb;
 
+// OBB_DISPATCH_DTYPE with the head layout (a value loss_check accepted) bound to the constant LAY as well
+#define LOSS_DISPATCH(dtype, layout, T, LAY, ...)                                                                                  \
+  OBB_DISPATCH_DTYPE(dtype, T, if ((layout) == kConv) { constexpr int LAY = kConv; __VA_ARGS__; }                                  \
+                               else { constexpr int LAY = kRows; __VA_ARGS__; })
+
 extern "C" {
 
 size_t obb_loss_workspace_bytes(const obb_loss_config* cfg, int64_t nt) {
@@ -673,8 +789,8 @@ int obb_loss_forward(const obb_loss_config* cfg, const void* const* p_levels_hos
   rc = run_match(cfg, cv, d, st);
   if (rc) return rc;
   dim3 gd(kDenseBlocks, cfg->nl);
-  OBB_DISPATCH_DTYPE(dtype, T, k_loss_dense_fwd<T><<<gd, 256, 0, st>>>(cv.dev));
-  if (d.cap > 0) OBB_DISPATCH_DTYPE(dtype, T, k_loss_entries_fwd<T><<<entry_grid(d), 256, 0, st>>>(cv.dev));
+  LOSS_DISPATCH(dtype, cfg->head_layout, T, LAY, k_loss_dense_fwd<T, LAY><<<gd, 256, 0, st>>>(cv.dev));
+  if (d.cap > 0) LOSS_DISPATCH(dtype, cfg->head_layout, T, LAY, k_loss_entries_fwd<T, LAY><<<entry_grid(d), 256, 0, st>>>(cv.dev));
   k_loss_finalize<<<cfg->nl, 1024, 0, st>>>(cv.dev, cv.lvl_out, cv.counts + kLv + 1);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
@@ -697,8 +813,9 @@ int obb_loss_backward(const obb_loss_config* cfg, const void* const* p_levels_ho
   }
   k_loss_setup<<<1, 256, 0, st>>>(d, cv.dev);
   dim3 gd(2048, cfg->nl);
-  OBB_DISPATCH_DTYPE(dtype, T, k_loss_bwd_dense<T><<<gd, 256, 0, st>>>(cv.dev));
-  if (d.cap > 0) OBB_DISPATCH_DTYPE(dtype, T, k_loss_entries_bwd<T><<<entry_grid(d), 256, 0, st>>>(cv.dev));
+  if (cfg->head_layout == kConv) OBB_DISPATCH_DTYPE(dtype, T, k_loss_bwd_dense_conv<T><<<gd, 256, 0, st>>>(cv.dev));
+  else OBB_DISPATCH_DTYPE(dtype, T, k_loss_bwd_dense<T><<<gd, 256, 0, st>>>(cv.dev));
+  if (d.cap > 0) LOSS_DISPATCH(dtype, cfg->head_layout, T, LAY, k_loss_entries_bwd<T, LAY><<<entry_grid(d), 256, 0, st>>>(cv.dev));
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 

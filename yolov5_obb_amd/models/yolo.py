@@ -50,7 +50,11 @@ class Detect(nn.Module):
     # augmented inference (forward_augment below, Model._forward_augment under dropin.install()): the three passes' surviving
     # levels decoded, de-scaled, de-flipped and concatenated by ONE launch of obb_detect_decode_tta.  Opt-in like lazy_nms.
     fused_tta = False
-    _collect = False         # set by forward_augment around its passes: forward() returns the conv outputs
+    # training mode on the GPU: return the permuted heads as VIEWS of the conv outputs (same shape, dtype and values, no
+    # transposing copy).  ComputeLoss reads them where they lie and writes the gradient straight into the conv layout
+    # (OBB_LOSS_LAYOUT_CONV); any other consumer sees ordinary strided tensors.  Opt-in like lazy_nms.
+    lazy_train = False
+    _collect = False        # set by forward_augment around its passes: forward() returns the conv outputs
 
     def __init__(self, nc=80, anchors=(), ch=(), inplace=True):  # detection layer
         super().__init__()
@@ -107,7 +111,9 @@ class Detect(nn.Module):
             for i in range(self.nl):
                 x[i] = self.m[i](x[i])  # conv
                 bs, _, ny, nx = x[i].shape
-                x[i] = x[i].view(bs, self.na, self.no, ny, nx).permute(0, 1, 3, 4, 2).contiguous()
+                x[i] = x[i].view(bs, self.na, self.no, ny, nx).permute(0, 1, 3, 4, 2)
+                if not (self.lazy_train and x[i].is_cuda):
+                    x[i] = x[i].contiguous()
             return x
 
         if not x[0].is_cuda:

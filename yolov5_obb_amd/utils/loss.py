@@ -4,7 +4,9 @@ Same constructor, attributes (``hyp, gr, balance, autobalance, sort_obj_iou, ssi
 call signature and return values as the reference, so ``train.py:269,326`` and ``val.py:199`` run unchanged.  The work is
 done by the loss entry points of libobb_hip.so (``obb_loss_forward`` / ``obb_loss_backward`` / ``obb_loss_build_targets``,
 include/obb_hip.h) behind one ``torch.autograd.Function``: no per-level Python loop, no boolean-mask gathers, no host
-synchronisation, one write of the gradient tensors.
+synchronisation, one write of the gradient tensors.  Head outputs that are the permuted VIEWS of the 1x1 convs' outputs
+(``Detect.lazy_train``) are read where they lie and the gradient is written in the conv layout (``is_conv_view``,
+``OBB_LOSS_LAYOUT_CONV``): same bits, no transposing copy on either side of the loss.
 """
 import ctypes as C
 
@@ -24,7 +26,11 @@ class _LossConfig(C.Structure):
                 ("anchor_t", C.c_float), ("cp", C.c_float), ("cn", C.c_float),
                 ("cls_pw", C.c_float), ("theta_pw", C.c_float), ("obj_pw", C.c_float),
                 ("gain_box", C.c_float), ("gain_obj", C.c_float), ("gain_cls", C.c_float), ("gain_theta", C.c_float),
-                ("gr", C.c_float), ("sort_obj_iou", C.c_int32), ("csl_radius", C.c_float), ("fl_gamma", C.c_float)]
+                ("gr", C.c_float), ("sort_obj_iou", C.c_int32), ("csl_radius", C.c_float), ("fl_gamma", C.c_float),
+                ("head_layout", C.c_int32)]
+
+
+LAYOUT_ROWS, LAYOUT_CONV = 0, 1      # OBB_LOSS_LAYOUT_* of include/obb_hip.h
 
 
 def smooth_BCE(eps=0.1):  # utils/loss.py:13-15
@@ -44,6 +50,20 @@ def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+def is_conv_view(t, na=None):
+    """True when the (bs, na, ny, nx, no) head output `t` is the permuted VIEW of a 1x1-conv output, i.e. of one dense
+    (bs, na*no, ny, nx) block that starts on a 16-byte boundary: `conv.view(bs, na, no, ny, nx).permute(0, 1, 3, 4, 2)`, what
+    Detect.forward returns in training mode under Detect.lazy_train.  The kernels then read it where it lies
+    (OBB_LOSS_LAYOUT_CONV).  A dimension of size 1 may carry any stride.  Pure: reads sizes, strides and the address only."""
+    if t.dim() != 5 or t.numel() == 0 or (na is not None and t.shape[1] != na):
+        return False
+    bs, na_, ny, nx, no = t.shape
+    want = (na_ * no * ny * nx, no * ny * nx, nx, 1, ny * nx)
+    if any(n != 1 and s != w for n, s, w in zip(t.shape, t.stride(), want)):
+        return False
+    return t.data_ptr() % 16 == 0
+
+
 class _ObbLossFn(torch.autograd.Function):
     """loss_out = obb_loss_forward(p, targets); d loss_out[0] / d p[i] = obb_loss_backward(...)."""
 
@@ -55,9 +75,13 @@ class _ObbLossFn(torch.autograd.Function):
             if pi.dtype != p[0].dtype or pi.device != dev:
                 raise RuntimeError(f"ComputeLoss: p[{i}] is {pi.dtype} on {pi.device}, p[0] is {p[0].dtype} on {dev}: "
                                    "all head outputs must share dtype and device")
-        ps = [pi.contiguous() for pi in p]
+        # every level the permuted view of its conv output (Detect.lazy_train): read where it lies, nothing is copied and the
+        # views themselves are saved.  Anything else (a mix, channels-last, a sliced base): the contiguous row layout, as before
+        conv = all(is_conv_view(pi) for pi in p)
+        ps = list(p) if conv else [pi.contiguous() for pi in p]
         tg = targets.to(device=dev, dtype=torch.float32).contiguous()
         cfg = owner._config(ps)
+        cfg.head_layout = LAYOUT_CONV if conv else LAYOUT_ROWS
         nt, tcols = int(tg.shape[0]), int(tg.shape[1]) if tg.dim() == 2 else 0
         L = _lib.lib()
         out = torch.empty(5 + _MAX_LV, dtype=torch.float32, device=dev)
@@ -78,12 +102,19 @@ class _ObbLossFn(torch.autograd.Function):
     def backward(ctx, gloss, _gout):
         tg, *ps = ctx.saved_tensors
         dev = ps[0].device
-        grads = [torch.empty_like(pi) for pi in ps]
+        if ctx.cfg.head_layout == LAYOUT_CONV:
+            # the conv outputs' own gradients, (bs, na*no, ny, nx) contiguous, returned with the views' strides: autograd's
+            # permute / view backward hand these very buffers to the conv's backward, nothing transposes them
+            dims = [(pi.shape[0], pi.shape[1], pi.shape[4], pi.shape[2], pi.shape[3]) for pi in ps]
+            bufs = [pi.new_empty((b, na * no, ny, nx)) for pi, (b, na, no, ny, nx) in zip(ps, dims)]
+            grads = [g.view(d).permute(0, 1, 3, 4, 2) for g, d in zip(bufs, dims)]
+        else:
+            bufs = grads = [torch.empty_like(pi) for pi in ps]
         gscale = gloss.reshape(-1)[:1].to(torch.float32).contiguous()
         L = _lib.lib()
         with _lib.guard(dev):
             rc = L.obb_loss_backward(C.byref(ctx.cfg), _ptr_array(ps), ctx.code, _lib.ptr(tg), int(tg.shape[0]),
-                                     int(tg.shape[1]) if tg.dim() == 2 else 0, _lib.ptr(gscale), _ptr_array(grads),
+                                     int(tg.shape[1]) if tg.dim() == 2 else 0, _lib.ptr(gscale), _ptr_array(bufs),
                                      _lib.ptr(ctx.ws), ctx.ws.numel(), _lib.stream_ptr(dev))
         _lib.check(rc, "obb_loss_backward")
         return (None, None, *grads)
