@@ -363,7 +363,7 @@ int obb_non_max_suppression_obb_head(int nl, const void* const* conv_out, int dt
                                      int64_t* out_count, int64_t* status, void* ws, size_t ws_bytes, void* state, size_t state_bytes,
                                      void* stream);
 
-/* The caller's side of the four fused entries above, as host code (csrc/nmsobb_hints.h: no device call, no allocation, no state
+/* The caller's side of the fused entries (the four above and obb_non_max_suppression_obb_tta_head below), as host code (csrc/nmsobb_hints.h: no device call, no allocation, no state
  * but the struct): the reference implementation of what to do around a call, used by both bindings of this repository.  A caller
  * keeps one obb_nms_obb_hints per input shape (and per thread, device and conf_thres: other batches say nothing about this one's).
  *
@@ -559,6 +559,35 @@ typedef struct obb_tta_pass {
 } obb_tta_pass;
 int obb_detect_decode_tta(int npass, const obb_tta_pass* passes_host, int dtype, int64_t bs, int64_t na, int64_t no, void* z_out,
                           int64_t a_total, void* objcol_out, void* stream);
+
+/* Augmented inference followed by non_max_suppression_obb, fed straight from the passes' conv outputs: obb_detect_decode_tta and
+ * obb_non_max_suppression_obb_st as val.py --augment / detect.py --augment chain them, without the dense prediction tensor z
+ * (bs, a_total, no) in between -- obb_non_max_suppression_obb_head over (pass, level) entries.
+ *   passes_host  as for obb_detect_decode_tta: every pass lists only the levels that SURVIVE the clip, in order; at most
+ *                OBB_TTA_MAX_PASSES * OBB_DETECT_MAX_LEVELS = 16 entries.  a_total: the rows of torch.cat(_clip_augmented(y), 1).
+ * What is read: per (entry, image, anchor) tile of 256 bytes of positions, the objectness line (channel a*no + 4; the de-scale does
+ * not touch it) -- decoded exactly as z[..., 4] and compared with conf_thres in the tensor dtype -- and, only where some position of
+ * the tile passes, the tile's no channel lines.  The passing rows are decoded with the arithmetic of obb_detect_decode, their box
+ * channels 0..3 de-scaled with (float)(1.0 / scale) and de-flipped with the rounding points of obb_detect_decode_tta
+ * (csrc/detect_math.h), and reduced as the filter kernel of obb_non_max_suppression_obb reduces rows of z.  The channel lines of an
+ * entry are loaded 16 or 8 bytes at a time when its conv output and its planes (ny*nx elements) lie on such boundaries, element-wise
+ * otherwise -- chosen per entry.  Every candidate carries the row it has in the concatenated z (an entry starts at the rows of the
+ * entries before it, then a*ny*nx + y*nx + x), so the sort keys, the score ties and the kept list are those of the eager chain: the
+ * result is bit-identical to obb_detect_decode_tta (z_out) followed by obb_non_max_suppression_obb_st on the same inputs and arguments.
+ * Workspace: ws_size = obb_nms_obb_workspace_bytes(bs, cap_img, nc, agnostic) bytes with A = a_total -- nothing more; ws / ws_size
+ * follow the rules of ws / ws_bytes of the other entries (256-byte aligned, OBB_ERR_WORKSPACE before any device call).  Output
+ * contract, status words, hints and retry cases as obb_non_max_suppression_obb_st; `state` may be NULL (as in
+ * obb_non_max_suppression_obb_head).
+ * OBB_ERR_BAD_ARG before any device call (host code, csrc/tta_head_plan.h) for: npass outside 1..OBB_TTA_MAX_PASSES, a pass's nl
+ * outside 1..OBB_DETECT_MAX_LEVELS, a flip other than 0 / 2 / 3, a scale <= 0 or not finite, an image size < 1, NULL passes or a NULL
+ * listed conv_out, na outside 1..OBB_LOSS_MAX_ANCHORS, nc = no - 185 outside 1..256, an unknown dtype, bs * na > 65535, a_total
+ * smaller than the rows listed, a_total * nc past the 32-bit row field of the sort key, more tiles than the grid holds. */
+int obb_non_max_suppression_obb_tta_head(int npass, const obb_tta_pass* passes_host, int dtype, int64_t bs, int64_t na, int64_t no,
+                                         int64_t a_total, float conf_thres, float iou_thres, const int32_t* classes_host, int n_classes,
+                                         int agnostic, int multi_label, int64_t max_det, int64_t max_nms, float max_wh, const float* extra8,
+                                         int64_t n_extra, int64_t cap_img, int64_t expected_cand, float* out, int out_packed,
+                                         int64_t* out_count, int64_t* status, void* ws, size_t ws_size, void* state, size_t state_bytes,
+                                         void* stream);
 
 /* gaussian_label_cpu (utils/rboxs_utils.py:9-26) for n angles at once: out [n][num_class] fp32, evaluated in double. */
 int obb_csl_encode_f32(const float* labels, int64_t n, int num_class, double u, double sig, float* out, void* stream);

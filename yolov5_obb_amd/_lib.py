@@ -55,6 +55,8 @@ SIGNATURES = {
                                               _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "obb_non_max_suppression_obb_head": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _i32, _i32, _i32,
                                                 _i64, _i64, _f32, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "obb_non_max_suppression_obb_tta_head": (_i32, [_i32, _vp, _i32, _i64, _i64, _i64, _i64, _f32, _f32, _vp, _i32, _i32, _i32,      # passes: TtaPass array
+                                                    _i64, _i64, _f32, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "obb_nms_obb_hints_init": (None, [_vp]),                        # hints: NmsObbHints (below), host memory
     "obb_nms_obb_hints_cap": (_i64, [_vp, _i64]),
     "obb_nms_obb_hints_word": (_i64, [_vp]),

@@ -1059,6 +1059,20 @@ int obb_non_max_suppression_obb_head(int nl, const void* const* conv_out, int dt
                      (hipStream_t)stream, state, state_bytes, &h);
 }
 
+int obb_non_max_suppression_obb_tta_head(int npass, const obb_tta_pass* passes_host, int dtype, int64_t bs, int64_t na, int64_t no,
+                                         int64_t a_total, float conf_thres, float iou_thres, const int32_t* classes_host, int n_classes,
+                                         int agnostic, int multi_label, int64_t max_det, int64_t max_nms, float max_wh, const float* extra8,
+                                         int64_t n_extra, int64_t cap_img, int64_t expected_cand, float* out, int out_packed,
+                                         int64_t* out_count, int64_t* status, void* ws, size_t ws_size, void* state, size_t state_bytes,
+                                         void* stream) {
+  // the limits of obb_detect_decode_tta and obb_non_max_suppression_obb_head, checked in host code (tta_head_plan.h) before anything is launched
+  HeadFrontTta h;
+  if (const int rc = head_tta_build(npass, passes_host, dtype, bs, na, no, a_total, &h, nullptr)) return rc;
+  return run_nms_obb(nullptr, nullptr, dtype, bs, a_total, no, conf_thres, iou_thres, classes_host, n_classes, agnostic, multi_label, max_det,
+                     max_nms, max_wh, extra8, n_extra, cap_img, expected_cand, out, out_packed ? 1 : 0, out_count, status, ws, ws_size,
+                     (hipStream_t)stream, state, state_bytes, nullptr, &h);
+}
+
 int obb_profile_enable(int on) {
   g_prof.on = on == 2 ? 2 : (on != 0 ? 1 : 0);
   g_prof.used = 0;

@@ -13,8 +13,17 @@
 //   phase 2  the tile's no channel lines (256 bytes each) are staged in LDS, and each passing position is reduced from there by a
 //            16-lane group exactly as k_decode's reduce_quad reduces a row of z.  Rows of z are numbered as Detect numbers them,
 //            a_off[level] + a*ny*nx + p: the sort keys, and with them tie order and kept list, are those of the eager chain.
+//
+// k_decode_head<T, true> is the front kernel of obb_non_max_suppression_obb_tta_head (augmented inference, models/yolo.py:149-209):
+// the same workgroup over the (pass, level) entries of HeadFrontTta (tta_head_plan.h) instead of the levels of HeadFront.  What differs:
+// the table is searched over up to 16 entries; the load width of phase 2a is the ENTRY's (16, 8 bytes or element-wise); the four box
+// channels go through detect_descale_one with the entry's inv_scale / flip / image size after detect_decode_one, as
+// k_detect_decode_tta writes them into z (channel 4 and above are not de-scaled: phase 1 is the same).  a_off[entry] is the row the
+// entry starts at in torch.cat(_clip_augmented(y), 1), so keys, tie order and kept list are those of obb_detect_decode_tta followed
+// by the eager NMS.  Everything under `if constexpr (TTA)` is compiled into that instantiation only.
 #pragma once
 #include "detect_math.h"
+#include "tta_head_plan.h"
 
 namespace obb {
 
@@ -38,14 +47,18 @@ struct HeadFront {
 };
 
 typedef unsigned int head_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int head_u32x2 __attribute__((ext_vector_type(2)));
 
 template <typename T>
 __device__ __forceinline__ float head_ld(const uint32_t* tile, int c, int p) {          // channel c, position p of the staged tile
   return ld_as_float<T>(reinterpret_cast<const T*>(tile + c * kHeadPitchDw) + p);
 }
 
-template <typename T>
-__global__ __launch_bounds__(kHeadThreads) void k_decode_head(DecodeArgs a, HeadFront h) {
+template <bool TTA> struct HeadFrontOf { typedef HeadFront type; };
+template <> struct HeadFrontOf<true> { typedef HeadFrontTta type; };
+
+template <typename T, bool TTA = false>
+__global__ __launch_bounds__(kHeadThreads) void k_decode_head(DecodeArgs a, typename HeadFrontOf<TTA>::type h) {
   constexpr int TP = kHeadTile<T>;
   extern __shared__ __attribute__((aligned(16))) uint32_t s_tile[];                    // [no][kHeadPitchDw]
   __shared__ float4 s_c0[kHeadWaves][kHeadStage], s_c1[kHeadWaves][kHeadStage];
@@ -99,7 +112,32 @@ __global__ __launch_bounds__(kHeadThreads) void k_decode_head(DecodeArgs a, Head
   if (n_rows == 0) return;                                       // (workgroup-uniform)
 
   // ---- phase 2a: the tile's channel lines into LDS (coalesced along p)
-  if (h.vec) {
+  int vec;                                                       // (workgroup-uniform)
+  if constexpr (TTA) vec = h.vec[l]; else vec = h.vec;
+  if (TTA && vec == 8) {
+    if constexpr (TTA) {                                        // 8-byte pieces, 32 per full line: planes on 8-byte boundaries (54x54 fp16)
+      constexpr int E = 8 / (int)sizeof(T);
+      constexpr int kBatch = 8;
+      const int q = tid & 31, c8 = tid >> 5;
+      const bool live = q * E < nt;                              // (nt is a multiple of E on this path)
+      for (int c0 = c8; c0 < no; c0 += 8 * kBatch) {
+        head_u32x2 v[kBatch];
+#pragma unroll
+        for (int u = 0; u < kBatch; u++) {
+          const int c = c0 + u * 8;
+          if (c < no && live) v[u] = __builtin_nontemporal_load(reinterpret_cast<const head_u32x2*>(in + (size_t)c * HW) + q);
+        }
+#pragma unroll
+        for (int u = 0; u < kBatch; u++) {
+          const int c = c0 + u * 8;
+          if (c < no && live) {
+            uint32_t* d = s_tile + c * kHeadPitchDw + q * 2;
+            d[0] = v[u].x; d[1] = v[u].y;
+          }
+        }
+      }
+    }
+  } else if (vec) {
     constexpr int E = 16 / (int)sizeof(T);                       // elements per 16-byte piece; 16 pieces per full line
     constexpr int kBatch = 8;
     const int q = tid & 15, c16 = tid >> 4;
@@ -179,6 +217,12 @@ __global__ __launch_bounds__(kHeadThreads) void k_decode_head(DecodeArgs a, Head
     float box[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) box[k] = valid ? detect_decode_one<T>(head_ld<T>(s_tile, k, p), k, gx, gy, stride, aw, ah) : 0.f;
+    if constexpr (TTA) {                                         // _descale_pred on the decoded box, as k_detect_decode_tta writes z[..., :4]
+      const float inv_scale = h.inv_scale[l], img_w = h.img_w[l], img_h = h.img_h[l];
+      const int flip = h.flip[l];
+#pragma unroll
+      for (int k = 0; k < 4; k++) box[k] = valid ? detect_descale_one<T>(box[k], k, inv_scale, flip, img_w, img_h) : 0.f;
+    }
     const float bx_ = box[0], by = box[1], bl = box[2], bs_ = box[3];
     const int bflags = cand_flags(bx_, bl, bs_, a.win_lo, a.win_hi);
     const long long rw = row0 + p;
@@ -233,20 +277,24 @@ __global__ __launch_bounds__(kHeadThreads) void k_decode_head(DecodeArgs a, Head
 static size_t head_lds_bytes(int64_t no) { return (size_t)no * kHeadPitchDw * 4; }
 
 // the launch run_nms_obb makes in place of k_decode (grid: the levels' tiles x bs*na)
-static int launch_decode_head(const HeadFront& h, const DecodeArgs& d, int dtype, hipStream_t st) {
+template <bool TTA>
+static int launch_decode_head_of(const typename HeadFrontOf<TTA>::type& h, const DecodeArgs& d, int dtype, hipStream_t st) {
   static OncePerDevice attr;
   if (const int attr_dev = attr.need(); attr_dev != OncePerDevice::kDone) {
     const int lds = (int)head_lds_bytes(5 + 256 + 180);
-    if (hipFuncSetAttribute((const void*)k_decode_head<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_decode_head<__half>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_decode_head<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)k_decode_head<float, TTA>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_decode_head<__half, TTA>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_decode_head<bf16_t, TTA>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
       return OBB_ERR_LAUNCH;
     attr.mark(attr_dev);
   }
   const dim3 grid((unsigned)h.tile_end[h.nl - 1], (unsigned)(d.bs * h.na));
   const size_t lds = head_lds_bytes(d.no);
-  OBB_DISPATCH_DTYPE(dtype, T, k_decode_head<T><<<grid, kHeadThreads, lds, st>>>(d, h));
+  OBB_DISPATCH_DTYPE(dtype, T, k_decode_head<T, TTA><<<grid, kHeadThreads, lds, st>>>(d, h));
   return OBB_OK;
 }
+static int launch_decode_head(const HeadFront& h, const DecodeArgs& d, int dtype, hipStream_t st) { return launch_decode_head_of<false>(h, d, dtype, st); }
+// ... over the (pass, level) entries of augmented inference
+static int launch_decode_head_tta(const HeadFrontTta& h, const DecodeArgs& d, int dtype, hipStream_t st) { return launch_decode_head_of<true>(h, d, dtype, st); }
 
 }  // namespace obb

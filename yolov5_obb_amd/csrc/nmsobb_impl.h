@@ -1381,16 +1381,19 @@ static ObbCarve obb_carve(void* base, int64_t bs, int64_t cap_img, int64_t ncs) 
 
 // The front kernel that reads the Detect head's conv outputs instead of `pred` (nms_head.h, obb_non_max_suppression_obb_head)
 struct HeadFront;
+struct HeadFrontTta;
 static int launch_decode_head(const HeadFront& h, const DecodeArgs& d, int dtype, hipStream_t st);
+static int launch_decode_head_tta(const HeadFrontTta& h, const DecodeArgs& d, int dtype, hipStream_t st);
 
-// head != NULL: the candidates come from the conv outputs it describes (k_decode_head) and pred / objcol are not read
+// head != NULL: the candidates come from the conv outputs it describes (k_decode_head) and pred / objcol are not read;
+// tta != NULL: from the (pass, level) entries of augmented inference (k_decode_head<T, true>), likewise
 static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t bs, int64_t A, int64_t no, float conf_thres, float iou_thres,
                        const int32_t* classes_host, int n_classes, int agnostic, int multi_label, int64_t max_det, int64_t max_nms,
                        float max_wh, const float* extra8, int64_t n_extra, int64_t cap_img, int64_t expected_cand, float* out,
                        int out_packed, int64_t* out_count, int64_t* status, void* ws, size_t ws_bytes, hipStream_t st, void* state = nullptr,
-                       size_t state_bytes = 0, const HeadFront* head = nullptr) {
+                       size_t state_bytes = 0, const HeadFront* head = nullptr, const HeadFrontTta* tta = nullptr) {
   const int nc = (int)(no - 5 - 180);                              // :784
-  if (bs < 1 || A < 1 || nc < 1 || nc > 256 || max_det < 1 || cap_img < 1 || (!pred && !head) || !out || !out_count || !status)
+  if (bs < 1 || A < 1 || nc < 1 || nc > 256 || max_det < 1 || cap_img < 1 || (!pred && !head && !tta) || !out || !out_count || !status)
     return OBB_ERR_BAD_ARG;
   if (A * nc + n_extra > 0xffffffffLL || bs * cap_img > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
   if (!dtype_known(dtype)) return OBB_ERR_BAD_ARG;
@@ -1445,8 +1448,8 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   dim3 gd((unsigned)((A + kDecThreads * d.rows_per_thread - 1) / (kDecThreads * d.rows_per_thread)), (unsigned)bs);
   {
     ProfScope ps(PROF_DECODE, st);
-    if (head) {
-      rc = launch_decode_head(*head, d, dtype, st);
+    if (head || tta) {
+      rc = head ? launch_decode_head(*head, d, dtype, st) : launch_decode_head_tta(*tta, d, dtype, st);
       if (rc) return rc;
     } else OBB_DISPATCH_DTYPE(dtype, T, k_decode<T><<<gd, kDecThreads, 0, st>>>(d));
   }

@@ -36,7 +36,8 @@ namespace {
 // ---------------------------------------------------------------- the C ABI, bound at run time
 #define OBB_API(X)                                                                                                         \
   X(obb_version) X(obb_nms_set_max_grid) X(obb_nms_workspace_bytes) X(obb_nms_rotated_f32) X(obb_nms_rotated_f64)       \
-  X(obb_nms_poly_f32) X(obb_nms_obb_workspace_bytes) X(obb_nms_obb_state_bytes) X(obb_non_max_suppression_obb_st) X(obb_non_max_suppression_obb_head)                                   \
+  X(obb_nms_poly_f32) X(obb_nms_obb_workspace_bytes) X(obb_nms_obb_state_bytes) X(obb_non_max_suppression_obb_st) X(obb_non_max_suppression_obb_head) \
+  X(obb_non_max_suppression_obb_tta_head)                                                                                  \
   X(obb_nms_obb_hints_init) X(obb_nms_obb_hints_cap) X(obb_nms_obb_hints_word) X(obb_nms_obb_hints_update)                \
   X(obb_val_tail_batch_workspace_bytes) X(obb_val_tail_batch_rows_f32)
 
@@ -285,7 +286,7 @@ struct NmsOpts {
   }
 };
 
-// The call loop of both fused entries (obb_non_max_suppression_obb_st, obb_non_max_suppression_obb_head): workspace, caller-kept
+// The call loop of the fused entries (obb_non_max_suppression_obb_st, obb_non_max_suppression_obb_head, ..._tta_head): workspace, caller-kept
 // state, polled counters, and the shape's hints and retries as the library decides them (obb_nms_obb_hints_*).  launch(cap_img,
 // expected_cand, out, out_count, status, ws, ws_bytes, state, state_bytes, stream) makes one call of the entry with out_packed = 0.
 template <class Launch>
@@ -436,6 +437,66 @@ std::vector<at::Tensor> non_max_suppression_obb_head(const std::vector<at::Tenso
                                                                  o.cls.empty() ? nullptr : o.cls.data(), (int)o.cls.size(), agnostic ? 1 : 0,
                                                                  multi ? 1 : 0, max_det, kMaxNms, (float)kMaxWh, o.extra_p, o.n_extra, cap,
                                                                  hint_word, out, 0, counts, status, ws, ws_bytes, state, state_bytes, st);
+                   });
+}
+
+// Augmented inference + non_max_suppression_obb straight from the passes' conv outputs (obb_non_max_suppression_obb_tta_head): the lazy
+// output of Detect.lazy_tta (models/yolo.py forward_augment).  Per listed pass p: convs[p] its surviving levels (bs, na*no, ny, nx)
+// contiguous, scales[p], flips[p] (0 / 2 / 3), anchors_px[p] [nl_p][na][2] flattened, strides[p] [nl_p]; a_total = the rows of
+// torch.cat(_clip_augmented(y), 1).  Same loop, hints and result as non_max_suppression_obb of that concatenation.
+std::vector<at::Tensor> non_max_suppression_obb_tta_head(const std::vector<std::vector<at::Tensor>>& convs, const std::vector<double>& scales,
+                                                         const std::vector<int64_t>& flips, const std::vector<std::vector<float>>& anchors_px,
+                                                         const std::vector<std::vector<float>>& strides, int64_t img_h, int64_t img_w, int64_t na,
+                                                         int64_t a_total, double conf_thres, double iou_thres,
+                                                         const c10::optional<std::vector<int64_t>>& classes, bool agnostic, bool multi_label,
+                                                         const c10::optional<at::Tensor>& extra, int64_t max_det) {
+  need_api();
+  const size_t np = convs.size();
+  if (np < 1 || np > OBB_TTA_MAX_PASSES || scales.size() != np || flips.size() != np || anchors_px.size() != np || strides.size() != np ||
+      na < 1 || na > OBB_LOSS_MAX_ANCHORS || convs[0].empty())
+    throw std::runtime_error("non_max_suppression_obb_tta_head: 1..4 passes with their scales, flips, anchors_px and strides expected");
+  const at::Tensor& c0 = convs[0][0];
+  require_cuda(c0, "convs[0][0]");
+  if (c0.dim() != 4 || c0.size(1) % na != 0) throw std::runtime_error("non_max_suppression_obb_tta_head: conv outputs (bs, na*no, ny, nx) expected");
+  const int64_t bs = c0.size(0), no = c0.size(1) / na, nc = no - 5 - kCsl;
+  if (nc < 1 || nc > 256) throw std::runtime_error("non_max_suppression_obb: 1 <= nc <= 256 supported, got nc = " + std::to_string(nc));
+  const int dtype = dtype_code(c0);
+  const at::Device dev = c0.device();
+  std::vector<obb_tta_pass> passes(np);
+  for (size_t p = 0; p < np; p++) {
+    obb_tta_pass& t = passes[p];
+    std::memset(&t, 0, sizeof(t));
+    const size_t nl = convs[p].size();
+    if (nl < 1 || nl > OBB_DETECT_MAX_LEVELS || strides[p].size() != nl || anchors_px[p].size() != nl * (size_t)na * 2)
+      throw std::runtime_error("non_max_suppression_obb_tta_head: 1..4 levels per pass with anchors_px [nl][na][2] and strides [nl] expected");
+    t.nl = (int32_t)nl; t.flip = (int32_t)flips[p]; t.scale = scales[p]; t.img_h = (int32_t)img_h; t.img_w = (int32_t)img_w;
+    for (size_t l = 0; l < nl; l++) {
+      const at::Tensor& c = convs[p][l];
+      if (c.device() != dev || c.scalar_type() != c0.scalar_type() || c.dim() != 4 || c.size(0) != bs || c.size(1) != na * no || !c.is_contiguous())
+        throw std::runtime_error("non_max_suppression_obb_tta_head: conv outputs of one device, dtype, batch and channel count, contiguous, expected");
+      t.conv_out[l] = c.data_ptr(); t.ny[l] = c.size(2); t.nx[l] = c.size(3); t.stride[l] = strides[p][l];
+      for (int64_t a = 0; a < na; a++) {
+        t.anchors_px[l][a][0] = anchors_px[p][(l * (size_t)na + (size_t)a) * 2];
+        t.anchors_px[l][a][1] = anchors_px[p][(l * (size_t)na + (size_t)a) * 2 + 1];
+      }
+    }
+  }
+  const bool multi = multi_label && nc > 1;
+  std::vector<at::Tensor> result;
+  if (bs == 0) return result;
+  NmsOpts o;
+  if (!o.prepare(classes, extra, dev)) {
+    result.assign((size_t)bs, at::zeros({0, 7}, at::TensorOptions().dtype(at::kFloat).device(dev)));
+    return result;
+  }
+  return run_fused(dev, bs, a_total, nc, multi, conf_thres, agnostic, max_det, o.n_extra,
+                   [&](int64_t cap, int64_t hint_word, float* out, int64_t* counts, int64_t* status, void* ws, size_t ws_bytes, void* state,
+                       size_t state_bytes, hipStream_t st) {
+                     return api.obb_non_max_suppression_obb_tta_head((int)np, passes.data(), dtype, bs, na, no, a_total, (float)conf_thres,
+                                                                     (float)iou_thres, o.cls.empty() ? nullptr : o.cls.data(), (int)o.cls.size(),
+                                                                     agnostic ? 1 : 0, multi ? 1 : 0, max_det, kMaxNms, (float)kMaxWh, o.extra_p,
+                                                                     o.n_extra, cap, hint_word, out, 0, counts, status, ws, ws_bytes, state,
+                                                                     state_bytes, st);
                    });
 }
 
@@ -609,6 +670,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("classes") = py::none(), py::arg("agnostic") = false, py::arg("multi_label") = false, py::arg("extra") = py::none(),
         py::arg("max_det") = 1500, py::arg("objcol") = py::none());
   m.def("non_max_suppression_obb_head", &non_max_suppression_obb_head, py::arg("convs"), py::arg("anchors_px"), py::arg("strides"),
+        py::arg("conf_thres") = 0.25, py::arg("iou_thres") = 0.45, py::arg("classes") = py::none(), py::arg("agnostic") = false,
+        py::arg("multi_label") = false, py::arg("extra") = py::none(), py::arg("max_det") = 1500);
+  m.def("non_max_suppression_obb_tta_head", &non_max_suppression_obb_tta_head, py::arg("convs"), py::arg("scales"), py::arg("flips"),
+        py::arg("anchors_px"), py::arg("strides"), py::arg("img_h"), py::arg("img_w"), py::arg("na"), py::arg("a_total"),
         py::arg("conf_thres") = 0.25, py::arg("iou_thres") = 0.45, py::arg("classes") = py::none(), py::arg("agnostic") = false,
         py::arg("multi_label") = false, py::arg("extra") = py::none(), py::arg("max_det") = 1500);
   m.def("abort_retries", []() { return (long long)g_abort_retries.load(std::memory_order_relaxed); },

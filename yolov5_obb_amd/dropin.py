@@ -11,7 +11,8 @@ What it does (INTEGRATION.md section 1 as code):
     modules, the hot-path objects by this package's (`non_max_suppression_obb`, `ComputeLoss`, `Detect`, `rbox2poly`,
     `poly2hbb`) -- scripts imported afterwards bind the replacements (`from utils.general import non_max_suppression_obb`);
   * wraps `models.yolo.Model._forward_augment` (`val.py --augment`): with `Detect.fused_tta` set and a GPU tensor the three passes
-    end in one `obb_detect_decode_tta` launch (`models.yolo.forward_augment` of this package); otherwise the reference's method;
+    end in one `obb_detect_decode_tta` launch (`models.yolo.forward_augment` of this package), with `Detect.lazy_tta` in a lazy
+    output that `non_max_suppression_obb` reads from the passes' conv outputs; otherwise the reference's method;
   * `uninstall()` puts everything back.
 Nothing of the reference is copied or modified on disk.
 
@@ -141,11 +142,12 @@ def install(patch_loaded_scripts=True, reference_cpu_ext=None):
     _set_attr(my_yolo.Detect, "__module__", "models.yolo")
     _set_attr(yolo, "Detect", my_yolo.Detect)           # parse_model resolves layer names in models.yolo's namespace
     # augmented inference (`val.py --augment`): with Detect.fused_tta on GPU tensors the three passes end in ONE decode launch
-    # (models.yolo.forward_augment of this package, resizing with the reference's own scale_img); otherwise the reference's method
+    # (models.yolo.forward_augment of this package, resizing with the reference's own scale_img), with Detect.lazy_tta in a lazy
+    # output for non_max_suppression_obb; otherwise the reference's method
     ref_augment = yolo.Model._forward_augment
 
     def _forward_augment(self, x):
-        if getattr(self.model[-1], "fused_tta", False) and _is_cuda(x):
+        if (getattr(self.model[-1], "fused_tta", False) or getattr(self.model[-1], "lazy_tta", False)) and _is_cuda(x):
             return my_yolo.forward_augment(self, x, scale_img=yolo.scale_img)
         return ref_augment(self, x)
 

@@ -15,7 +15,9 @@ tensor (a clone, a cast, the TTA concatenation, an in-place edit) takes the plai
 
 Augmented inference (``Model._forward_augment``, :149-209): ``forward_augment`` below.  With ``Detect.fused_tta`` the three passes'
 conv outputs are decoded, de-scaled, de-flipped and laid out like ``torch.cat(_clip_augmented(y), 1)`` by ONE launch of
-``obb_detect_decode_tta``, and the result keeps its objectness column (the concatenation of the eager chain loses it).
+``obb_detect_decode_tta``, and the result keeps its objectness column (the concatenation of the eager chain loses it).  With
+``Detect.lazy_tta`` nothing is launched at all: the result is a ``LazyTensor`` that ``non_max_suppression_obb`` reads straight from
+the passes' conv outputs (``obb_non_max_suppression_obb_tta_head``); any other use materialises the ``fused_tta`` tensor.
 """
 import collections
 import ctypes as C
@@ -54,6 +56,10 @@ class Detect(nn.Module):
     # transposing copy).  ComputeLoss reads them where they lie and writes the gradient straight into the conv layout
     # (OBB_LOSS_LAYOUT_CONV); any other consumer sees ordinary strided tensors.  Opt-in like lazy_nms.
     lazy_train = False
+    # augmented inference without the dense prediction tensor: forward_augment returns a lazy z (yolov5_obb_amd/lazy.py) that
+    # non_max_suppression_obb reads straight from the passes' conv outputs (obb_non_max_suppression_obb_tta_head); any other use
+    # materialises exactly the fused_tta tensor.  Needs neither fused_tta nor lazy_nms.  Opt-in.
+    lazy_tta = False
     _collect = False        # set by forward_augment around its passes: forward() returns the conv outputs
 
     def __init__(self, nc=80, anchors=(), ch=(), inplace=True):  # detection layer
@@ -177,7 +183,11 @@ class Detect(nn.Module):
     def _lazy_possible(self, convs):
         """lazy_nms applies: eval mode on the GPU (checked by the caller), grad disabled, version counters present (not under
         torch.inference_mode(), like couple_nms), and the limits of obb_non_max_suppression_obb_head."""
-        return (self.lazy_nms and not torch.is_grad_enabled() and not torch.is_inference_mode_enabled()
+        return self.lazy_nms and self._lazy_conditions(convs)
+
+    def _lazy_conditions(self, convs):
+        """What a lazy output needs whichever flag asks for it (lazy_nms, lazy_tta)."""
+        return (not torch.is_grad_enabled() and not torch.is_inference_mode_enabled()
                 and not any(torch.is_inference(c) for c in convs) and 1 <= self.nl <= _LAZY_MAX_LEVELS
                 and 1 <= self.na <= _LAZY_MAX_ANCHORS and 1 <= self.nc <= 256)
 
@@ -318,12 +328,8 @@ def scale_img(img, ratio=1.0, same_shape=False, gs=32):
 _scale_img = scale_img       # (forward_augment has a parameter of that name)
 
 
-def _decode_tta(det, convs_per_pass, plan, scales, flips, img_h, img_w):
-    """One obb_detect_decode_tta launch for the plan's surviving levels -> z (bs, a_total, no) with the objectness column."""
-    c0 = convs_per_pass[0][0]
-    code = _lib.dtype_code(c0, "forward_augment")
-    anchor_px, strides = det._host_tables()
-    bs, na = c0.shape[0], det.na
+def _tta_passes(convs_per_pass, plan, scales, flips, img_h, img_w, na, anchor_px, strides):
+    """The obb_tta_pass array of the plan's surviving levels (a pass that keeps no level is not listed)."""
     listed = [(k, p) for k, p in enumerate(plan.passes) if p.levels]
     arr = (_lib.TtaPass * len(listed))()
     for t, (k, p) in zip(arr, listed):
@@ -333,10 +339,21 @@ def _decode_tta(det, convs_per_pass, plan, scales, flips, img_h, img_w):
             t.conv_out[j], t.ny[j], t.nx[j], t.stride[j] = c.data_ptr(), c.shape[2], c.shape[3], strides[lv]
             for a in range(na):
                 t.anchors_px[j][a][0], t.anchors_px[j][a][1] = anchor_px[lv][2 * a], anchor_px[lv][2 * a + 1]
+    return arr
+
+
+def _decode_tta(det, convs_per_pass, plan, scales, flips, img_h, img_w, tables=None):
+    """One obb_detect_decode_tta launch for the plan's surviving levels -> z (bs, a_total, no) with the objectness column.
+    tables: (anchor_px, strides) read earlier (a lazy output's), or None for the head's current ones."""
+    c0 = convs_per_pass[0][0]
+    code = _lib.dtype_code(c0, "forward_augment")
+    anchor_px, strides = tables or det._host_tables()
+    bs, na = c0.shape[0], det.na
+    arr = _tta_passes(convs_per_pass, plan, scales, flips, img_h, img_w, na, anchor_px, strides)
     z = torch.empty((bs, plan.a_total, det.no), dtype=c0.dtype, device=c0.device)
     col = torch.empty((bs, plan.a_total), dtype=c0.dtype, device=c0.device) if det.couple_nms else None
     with torch.cuda.device(c0.device):
-        rc = _lib.lib().obb_detect_decode_tta(len(listed), C.cast(arr, C.c_void_p), code, bs, na, det.no, _lib.ptr(z), plan.a_total,
+        rc = _lib.lib().obb_detect_decode_tta(len(arr), C.cast(arr, C.c_void_p), code, bs, na, det.no, _lib.ptr(z), plan.a_total,
                                               _lib.ptr(col), _lib.stream_ptr(c0.device))
     _lib.check(rc, "obb_detect_decode_tta")
     if col is not None and not torch.is_inference(z):      # as in Detect.forward: no version counter, no column
@@ -344,13 +361,67 @@ def _decode_tta(det, convs_per_pass, plan, scales, flips, img_h, img_w):
     return z
 
 
+class LazyTtaHead:
+    """What a lazy forward_augment output keeps (Detect.lazy_tta): the passes' conv outputs with the version counters they had
+    when the passes ran, the plan, the passes' scales and flips, the image size and the host anchor / stride tables.  Like
+    LazyHead, the values the output stands for were fixed then: an in-place edit of a conv output makes any use raise."""
+    tta = True
+
+    def __init__(self, det, convs_per_pass, plan, scales, flips, img_h, img_w):
+        anchor_px, strides = det._host_tables()
+        self.det = det
+        self.convs = convs_per_pass
+        self.versions = [[c._version for c in cs] for cs in convs_per_pass]
+        self.plan, self.scales, self.flips = plan, [float(s) for s in scales], [int(f or 0) for f in flips]
+        self.img_h, self.img_w = int(img_h), int(img_w)
+        self.code = _lib.dtype_code(convs_per_pass[0][0], "forward_augment")
+        self.na, self.no, self.a_total = det.na, det.no, plan.a_total
+        self.anchor_px = [list(a) for a in anchor_px]           # [level][na * 2], pixels
+        self.strides = [float(s) for s in strides]
+        self.listed = [k for k, p in enumerate(plan.passes) if p.levels]
+
+    def check(self):
+        if [[c._version for c in cs] for cs in self.convs] != self.versions:
+            raise RuntimeError("forward_augment (lazy_tta): a conv output was modified in place after the passes ran; the prediction "
+                               "it stood for is gone -- keep the conv outputs unchanged until the output is used, or set lazy_tta = False")
+
+    def passes(self):
+        """The obb_tta_pass array of obb_non_max_suppression_obb_tta_head / obb_detect_decode_tta."""
+        return _tta_passes(self.convs, self.plan, self.scales, self.flips, self.img_h, self.img_w, self.na, self.anchor_px, self.strides)
+
+    def pass_lists(self):
+        """The same as plain lists for the compiled binding: per listed pass its surviving convs, scale, flip, anchors
+        [nl][na][2] flattened and strides [nl]."""
+        out = []
+        for k in self.listed:
+            lv = self.plan.passes[k].levels
+            out.append(([self.convs[k][i] for i in lv], self.scales[k], self.flips[k], [v for i in lv for v in self.anchor_px[i]],
+                        [self.strides[i] for i in lv]))
+        return out
+
+    def decode(self):
+        """The fused_tta tensor (the materialiser of the lazy output)."""
+        self.check()
+        return _decode_tta(self.det, self.convs, self.plan, self.scales, self.flips, self.img_h, self.img_w,
+                           tables=(self.anchor_px, self.strides))
+
+
+def _lazy_tta_output(det, convs_per_pass, plan, scales, flips, img_h, img_w):
+    """The lazy z of forward_augment; nothing is launched here."""
+    head = LazyTtaHead(det, convs_per_pass, plan, scales, flips, img_h, img_w)
+    c0 = convs_per_pass[0][0]
+    return LazyTensor((c0.shape[0], plan.a_total, det.no), c0.dtype, c0.device, head.decode, payload=head)
+
+
 def forward_augment(model, x, scales=(1, 0.83, 0.67), flips=(None, 3, None), scale_img=None):
     """Model._forward_augment of the reference for a model whose head is this package's Detect: (z, None).
 
     With Detect.fused_tta on GPU tensors the passes run with the head collecting its conv outputs, and ONE launch decodes,
     de-scales, de-flips and concatenates them (obb_detect_decode_tta): z is written once, in place, with the objectness column
-    attached.  fused_tta wins over lazy_nms here.  Otherwise -- fused_tta off, CPU tensors, nl > 4, a flip other than None / 2 / 3,
-    or a clip that does not fall on a level boundary (tta_plan) -- the reference's chain of torch ops on the eager passes; the
+    attached.  fused_tta wins over lazy_nms here.  With Detect.lazy_tta (and grad disabled, outside torch.inference_mode()) the same
+    passes are collected and z is a LazyTensor that launches nothing: non_max_suppression_obb reads the conv outputs
+    (obb_non_max_suppression_obb_tta_head), any other use materialises the fused_tta tensor.  Otherwise -- both flags off, CPU
+    tensors, nl > 4, a flip other than None / 2 / 3, or a clip that does not fall on a level boundary (tta_plan) -- the reference's chain of torch ops on the eager passes; the
     values are the same.  scale_img: the reference's utils.torch_utils.scale_img, or None for this module's.
     """
     det = model.model[-1]
@@ -362,10 +433,12 @@ def forward_augment(model, x, scales=(1, 0.83, 0.67), flips=(None, 3, None), sca
     def run(si, fi):
         return model._forward_once(resize(x.flip(fi) if fi else x, si, gs=gs))
 
-    fused = (getattr(det, "fused_tta", False) and x.is_cuda and not det.training and det.nl <= _lib.DETECT_MAX_LEVELS
-             and det.na <= _lib.MAX_ANCHORS and 1 <= len(passes) <= _lib.TTA_MAX_PASSES and all(fi in (None, 0, 2, 3) for _, fi in passes)
-             and all(si > 0 and math.isfinite(si) for si, _ in passes))
-    if fused:
+    level_wise = (x.is_cuda and not det.training and det.nl <= _lib.DETECT_MAX_LEVELS
+                  and det.na <= _lib.MAX_ANCHORS and 1 <= len(passes) <= _lib.TTA_MAX_PASSES and all(fi in (None, 0, 2, 3) for _, fi in passes)
+                  and all(si > 0 and math.isfinite(si) for si, _ in passes))
+    fused = getattr(det, "fused_tta", False) and level_wise
+    lazy = getattr(det, "lazy_tta", False) and level_wise and det._lazy_conditions(())
+    if fused or lazy:
         det._collect = True
         try:
             convs = [run(si, fi) for si, fi in passes]
@@ -373,8 +446,11 @@ def forward_augment(model, x, scales=(1, 0.83, 0.67), flips=(None, 3, None), sca
             del det._collect
         plan = tta_plan([[tuple(c.shape[2:]) for c in cs] for cs in convs], det.na, det.nl)
         if plan.on_boundary and plan.a_total > 0:
-            return _decode_tta(det, convs, plan, [s for s, _ in passes], [f for _, f in passes], img_h, img_w), None
-        y = [det._decode(cs, list(cs), allow_lazy=False)[0] for cs in convs]     # the cut splits a level: the chain, eagerly
+            if lazy and det._lazy_conditions([c for cs in convs for c in cs]):
+                return _lazy_tta_output(det, convs, plan, [s for s, _ in passes], [f for _, f in passes], img_h, img_w), None
+            if fused:
+                return _decode_tta(det, convs, plan, [s for s, _ in passes], [f for _, f in passes], img_h, img_w), None
+        y = [det._decode(cs, list(cs), allow_lazy=False)[0] for cs in convs]     # the cut splits a level (or lazy_tta alone cannot apply): the chain, eagerly
     else:
         y = [run(si, fi)[0] for si, fi in passes]
     return _augment_chain(y, passes, img_h, img_w, det.nl, getattr(model, "inplace", True)), None

@@ -132,7 +132,7 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
     """
     head = None
     if isinstance(prediction, LazyTensor):
-        # Detect.lazy_nms: never touched -> the fused entry on the conv outputs; materialised -> the real tensor, plain path
+        # Detect.lazy_nms / lazy_tta: never touched -> the fused entry on the conv outputs; materialised -> the real tensor, plain path
         head = prediction.payload
         if head is None:
             prediction = prediction.materialize()
@@ -165,6 +165,10 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
         cl = None
         if classes is not None:
             cl = [int(c) for c in (classes if isinstance(classes, (list, tuple)) else list(classes))]
+        if head is not None and getattr(head, "tta", False):       # models/yolo.py LazyTtaHead: the passes of augmented inference
+            convs, scales, flips, apx, strd = (list(v) for v in zip(*head.pass_lists()))
+            return ext.non_max_suppression_obb_tta_head(convs, scales, flips, apx, strd, head.img_h, head.img_w, head.na, head.a_total,
+                                                        float(conf_thres), float(iou_thres), cl, bool(agnostic), multi, extra, int(max_det))
         if head is not None:
             return ext.non_max_suppression_obb_head(head.convs, head.anchor_px, head.strides, float(conf_thres), float(iou_thres), cl,
                                                     bool(agnostic), multi, extra, int(max_det))
@@ -189,6 +193,15 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
             return L.obb_non_max_suppression_obb_col(
                 _lib.ptr(pred), _lib.ptr(col), dtype, bs, A, no, float(conf_thres), float(iou_thres), cls_p, n_cls, agn, int(multi),
                 max_det, _MAX_NMS, float(_MAX_WH), _lib.ptr(extra), n_extra, cap, hint_word, out, 1, counts, status, _lib.ptr(ws), ws.numel(), C.c_void_p(st))
+    elif getattr(head, "tta", False):
+        passes = head.passes()
+        passes_p = C.cast(passes, C.c_void_p)
+
+        def launch(cap, hint_word, out, counts, status, ws, st):
+            return L.obb_non_max_suppression_obb_tta_head(
+                len(passes), passes_p, dtype, bs, head.na, no, A, float(conf_thres), float(iou_thres), cls_p, n_cls,
+                agn, int(multi), max_det, _MAX_NMS, float(_MAX_WH), _lib.ptr(extra), n_extra, cap, hint_word, out, 1, counts, status,
+                _lib.ptr(ws), ws.numel(), None, 0, C.c_void_p(st))
     else:
         nl = head.nl
         conv_arr = (C.c_void_p * nl)(*[c.data_ptr() for c in head.convs])
@@ -206,7 +219,7 @@ def non_max_suppression_obb(prediction, conf_thres=0.25, iou_thres=0.45, classes
 
 
 def _run_fused(launch, dev, bs, A, nc, multi, conf_thres, n_extra, agn, max_det):
-    """The ctypes binding's call loop around one fused entry (launch: obb_non_max_suppression_obb_col or _head): workspace,
+    """The ctypes binding's call loop around one fused entry (launch: obb_non_max_suppression_obb_col, _head or _tta_head): workspace,
     polled counters, and the shape's hints and retries as the library decides them (include/obb_hip.h: obb_nms_obb_hints_*)."""
     L = _lib.lib()
     worst = A * (nc if multi else 1) + n_extra
