@@ -34,3 +34,16 @@ for binding in ("compiled" if _lib.compiled() is not None else "ctypes",):      
     torch.cuda.synchronize()
     t_tail = (time.perf_counter() - t0) / 200 * 1e3
     print(f"{binding:9s} non_max_suppression_obb (one tensor, warm) {t_nms:.4f} ms per batch | val_tail_batch {t_tail:.4f} ms per batch of 16 ({sum(len(d) for d in dets)} detections)", flush=True)
+# the same batch through the accumulating front ends (always the ctypes binding): enqueue time per call, the stream drained at the end
+from yolov5_obb_amd.utils.metrics import ConfusionMatrix
+vs, cm, cm2 = V.ValStats(obb=True, capacity=221 * sum(len(d) for d in dets)), ConfusionMatrix(16), ConfusionMatrix(16)
+for name, call in (("ValStats(obb=True).add_batch(confusion=cm)", lambda: vs.add_batch(dets, tg, shapes, iouv, confusion=cm)),
+                   ("ConfusionMatrix.add_batch", lambda: cm2.add_batch(dets, tg, shapes))):
+    for _ in range(20):
+        call()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(200):
+        call()
+    torch.cuda.synchronize()
+    print(f"{name} {(time.perf_counter() - t0) / 200 * 1e3:.4f} ms per batch of 16", flush=True)

@@ -283,6 +283,13 @@ def require_cuda(t, name):
                            f"(no CPU path, by design)")
 
 
+def require_cuda_preds(preds):
+    """require_cuda for every non-empty tensor of a batch's per-image detections."""
+    for p in preds:
+        if p.shape[0] and not p.is_cuda:
+            require_cuda(p, "pred")
+
+
 # ---- kept-count read-back through polled pinned memory (single-list NMS entry points)
 # The last kernel of a call writes the count with one aligned 8-byte store; the device reaches pinned host memory through the
 # same pointer, so the calling thread can poll it: no copy kernel behind the NMS, no wake-up of a blocked stream wait

@@ -501,7 +501,7 @@ std::vector<at::Tensor> non_max_suppression_obb_tta_head(const std::vector<std::
 }
 
 // ---------------------------------------------------------------- the post-NMS tail of val.py for a batch (val.py:209-250)
-constexpr int64_t kTailMaxBs = 64;       // csrc/head.hip kValTailMaxBs: images per obb_val_tail_batch_f32 call
+constexpr int64_t kTailMaxBs = 64;       // csrc/head.hip kValTailMaxBs: images per obb_val_tail_batch_f32 call (Python mirror: tail_batch.py)
 
 // shapes[j] = ((h, w), ((gain, gain), (pad_x, pad_y))) as LoadImagesAndLabels yields them -> {pad_x, pad_y, gain, w, h}
 void img5_of(const py::handle& shape_j, float* o) {

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..tail_batch import TailBatch
 
 NC_MAX = 256      # include/obb_hip.h: class ids are integers 0 .. 255
 MAX_NIOU = 16
@@ -155,14 +156,14 @@ class ConfusionMatrix:
                                                    _lib.ptr(mat), _lib.ptr(ws), ws.numel(), st)
         _lib.check(rc, "obb_confusion_process_batch_f32")
 
-    def _launch(self, L, det_ptr, doff, k, n, tg_ptr, nt, tcols, img5, dev, st):
-        """One obb_confusion_batch_f32 on arrays the caller has laid out for obb_val_tail_batch_f32 (<= 64 images)."""
-        mat = self._counters(dev)
-        if n == 0 or nt == 0:
+    def _launch(self, L, tb, ch, st):
+        """One obb_confusion_batch_f32 on a chunk (tail_batch.Chunk, with its img5) of the batch tb: <= 64 images."""
+        mat = self._counters(tb.device)
+        if ch.ntk == 0:
             return
-        ws = _lib.workspace(L.obb_confusion_workspace_bytes(n, nt), dev, st)
-        rc = L.obb_confusion_batch_f32(det_ptr, doff, k, tg_ptr, nt, tcols, img5, self.nc, float(self.conf), float(self.iou_thres),
-                                       _lib.ptr(mat), _lib.ptr(ws), ws.numel(), st)
+        ws = _lib.workspace(L.obb_confusion_workspace_bytes(ch.hi - ch.lo, ch.ntk), tb.device, st)
+        rc = L.obb_confusion_batch_f32(ch.part(tb.packed, 7), ch.doff, ch.k, ch.tg_ptr, ch.ntk, ch.tcols, ch.img5, self.nc,
+                                       float(self.conf), float(self.iou_thres), _lib.ptr(mat), _lib.ptr(ws), ws.numel(), st)
         _lib.check(rc, "obb_confusion_batch_f32")
 
     def add_batch(self, preds, targets, shapes):
@@ -170,46 +171,21 @@ class ConfusionMatrix:
         CUDA tensors [x y l s theta conf cls] (consecutive views of non_max_suppression_obb's packed buffer are used in place),
         targets (nt, >= 7) [img cls cx cy l s theta ...], shapes per image ((h, w), ((gain, gain), (pad_x, pad_y))).  The boxes
         are those of val.py:226-243 (pred_hbbn, labels_hbbn); images without detections or without labels add nothing."""
-        import ctypes as C
-        from ..val import _TAIL_MAX_BS, _as_f32_cuda, _pack_dets
-        bs = len(preds)
-        if bs == 0:
+        if len(preds) == 0:
             return
         _lib.require_cuda(preds[0], "pred")
         dev = preds[0].device
-        offs = [0] * (bs + 1)
-        for b in range(bs):
-            offs[b + 1] = offs[b] + preds[b].shape[0]
-        n = offs[bs]
         self._counters(dev)
-        tg = _as_f32_cuda(targets, dev) if targets.dim() == 2 and targets.shape[0] else None
-        if n == 0 or tg is None:
+        tb = TailBatch(preds, targets, dev)
+        if tb.n == 0 or tb.nt == 0:
             return
-        nt, tcols = tg.shape
-        packed = _pack_dets(preds, dev, n)
+        if not tb.in_place:
+            _lib.require_cuda_preds(preds)
         L = _lib.lib()
         with _lib.guard(dev):
             st = _lib.stream_handle(dev)
-            for b0 in range(0, bs, _TAIL_MAX_BS):
-                b1 = min(bs, b0 + _TAIL_MAX_BS)
-                k = b1 - b0
-                lo, hi = offs[b0], offs[b1]
-                if hi == lo:
-                    continue
-                doff = (C.c_int64 * (k + 1))(*[o - lo for o in offs[b0:b1 + 1]])
-                flat = []
-                for j in range(b0, b1):
-                    shape, ratio_pad = shapes[j][0], shapes[j][1]
-                    flat += (ratio_pad[1][0], ratio_pad[1][1], ratio_pad[0][0], shape[1], shape[0])
-                img5 = (C.c_float * (5 * k))(*flat)
-                tgk, ntk = tg, nt
-                if b0 or b1 < bs:                                # a chunk of a very large batch: its labels, re-based
-                    sel = (tg[:, 0] >= b0) & (tg[:, 0] < b1)
-                    tgk = tg[sel].clone()
-                    tgk[:, 0] -= b0
-                    ntk = int(tgk.shape[0])
-                self._launch(L, C.c_void_p(packed.data_ptr() + lo * 28), C.cast(doff, C.c_void_p), k, hi - lo,
-                             C.c_void_p(tgk.data_ptr()) if ntk else C.c_void_p(0), ntk, tcols, C.cast(img5, C.c_void_p), dev, st)
+            for ch in tb.chunks(shapes):
+                self._launch(L, tb, ch, st)
 
     @property
     def matrix(self):

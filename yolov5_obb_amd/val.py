@@ -2,9 +2,12 @@
 after ``non_max_suppression_obb`` -- ``rbox2poly`` -> ``poly2hbb`` -> ``xywh2xyxy`` -> ``scale_polys`` (val.py:226-236) and
 ``process_batch`` (val.py:69-90) -- as two fused launches of libobb_hip.so instead of ~15 small ATen kernels and a
 ``.cpu().numpy()`` round trip per image."""
+import threading
+
 import torch
 
 from . import _lib
+from .tail_batch import MAX_BS, TailBatch, as_f32, box_arrays, split_rows
 
 
 def val_postprocess(pred, ratio_pad=None, img1_shape=None, img0_shape=None):
@@ -75,9 +78,9 @@ def process_batch_obb(pred, labels, iouv, return_match=False):
     if labels.dim() != 2 or labels.shape[1] != 6:
         raise RuntimeError(f"process_batch_obb: labels must be (m,6), got {tuple(labels.shape)}")
     dev = pred.device
-    det = _as_f32_cuda(pred, dev)
-    lab = _as_f32_cuda(labels, dev)
-    iv = _as_f32_cuda(iouv, dev)
+    det = as_f32(pred, dev)
+    lab = as_f32(labels, dev)
+    iv = as_f32(iouv, dev)
     n, m, niou = det.shape[0], lab.shape[0], iv.shape[0]
     correct = torch.zeros((n, niou), dtype=torch.bool, device=dev)
     match_label = torch.full((n,), -1, dtype=torch.int32, device=dev)
@@ -91,54 +94,17 @@ def process_batch_obb(pred, labels, iouv, return_match=False):
     return (correct, match_label, match_iou) if return_match else correct
 
 
-_TAIL_MAX_BS = 64      # csrc/head.hip kValTailMaxBs: images per obb_val_tail_batch_f32 call
 _pin_cache = {}
-_arr_cache = {}
 
 
 def _pinned_rows(n, cols):
     """A pinned (n, cols) float32 view of a cached host buffer (per thread; grown geometrically)."""
-    import threading
     key = (threading.get_ident(), cols)
     buf = _pin_cache.get(key)
     if buf is None or buf.shape[0] < n:
         buf = torch.empty((max(1024, 2 * n), cols), dtype=torch.float32).pin_memory()
         _pin_cache[key] = buf
     return buf[:n]
-
-
-def _as_f32_cuda(t, dev):
-    """t as a contiguous float32 tensor on dev -- without a torch call when it already is one (the common case)."""
-    if t.dtype == torch.float32 and t.device == dev and t.is_contiguous():
-        return t
-    return t.to(device=dev, dtype=torch.float32).contiguous()
-
-
-def _pack_dets(preds, dev, n):
-    """The detections of a batch as ONE (n, 7) float32 array (None when n = 0): the split views of
-    non_max_suppression_obb's packed buffer in order, else a copy."""
-    packed, first = None, None
-    ok = True
-    for p in preds:
-        if p.shape[0] == 0:
-            continue
-        if p.device != dev or p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 7 or not p.is_contiguous():
-            if p.device.type != "cuda":
-                _lib.require_cuda(p, "pred")
-            ok = False
-            break
-        if first is None:
-            first, nxt = p, p.data_ptr()
-        if p.data_ptr() != nxt:
-            ok = False
-            break
-        nxt += p.shape[0] * 28
-    if n:
-        if ok and first is not None:
-            packed = first if first.shape[0] == n else torch.as_strided(first, (n, 7), (7, 1))
-        else:
-            packed = torch.cat([p.to(torch.float32) for p in preds], 0).contiguous()
-    return packed
 
 
 def val_tail_batch(preds, targets, shapes, iouv, want_boxes=False):
@@ -152,114 +118,52 @@ def val_tail_batch(preds, targets, shapes, iouv, want_boxes=False):
     shapes   per image (shape (h, w), ratio_pad ((gain, gain), (pad_x, pad_y))) as LoadImagesAndLabels yields them
     Returns  stats: per image (correct bool (n_i, niou), conf (n_i), cls (n_i)) on the HOST -- what val.py:250 appends -- and,
              with want_boxes, the packed device arrays (pred_poly, pred_hbb, pred_polyn, pred_hbbn) + the offsets."""
-    import ctypes as C
-    import threading
-    bs = len(preds)
-    if bs == 0:
+    if len(preds) == 0:
         return ([], None) if want_boxes else []
     ext = _lib.compiled()
     if ext is not None:          # the compiled binding builds the per-image tuples in C++ (csrc/torch_ext/nms_rotated_ext.cpp)
         return ext.val_tail_batch(list(preds), targets, shapes, iouv, bool(want_boxes))
+    _lib.require_cuda(preds[0], "pred")
     dev = preds[0].device
-    if dev.type != "cuda":
-        _lib.require_cuda(preds[0], "pred")
-    counts = [p.shape[0] for p in preds]
-    offs = [0] * (bs + 1)
-    for b in range(bs):
-        offs[b + 1] = offs[b] + counts[b]
-    n = offs[bs]
-    niou = iouv.shape[0]
-    packed = _pack_dets(preds, dev, n)
-    tg = _as_f32_cuda(targets, dev) if targets.dim() == 2 and targets.shape[0] else None
-    nt, tcols = (tg.shape[0], tg.shape[1]) if tg is not None else (0, 0)
-    iv = _as_f32_cuda(iouv, dev)
+    tb = TailBatch(preds, targets, dev)
+    if not tb.in_place:
+        _lib.require_cuda_preds(preds)
+    n, niou = tb.n, iouv.shape[0]
+    iv = as_f32(iouv, dev)
     host = _pinned_rows(n, niou + 2)                             # the kernels write the rows straight into it
-    boxes = None
-    if want_boxes:
-        boxes = (torch.empty((n, 10), dtype=torch.float32, device=dev), torch.empty((n, 6), dtype=torch.float32, device=dev),
-                 torch.empty((n, 10), dtype=torch.float32, device=dev), torch.empty((n, 6), dtype=torch.float32, device=dev))
+    boxes = box_arrays(n, dev) if want_boxes else None
     if n:
         L = _lib.lib()
-        null = C.c_void_p(0)
         with _lib.guard(dev):
             st = _lib.stream_handle(dev)
-            ws = _lib.workspace(L.obb_val_tail_batch_workspace_bytes(n, nt), dev, st)
+            ws = _lib.workspace(L.obb_val_tail_batch_workspace_bytes(n, tb.nt), dev, st)
             flag, flag_np = _lib.pinned_count(dev)
-            for b0 in range(0, bs, _TAIL_MAX_BS):                # (one call for any batch size val.py uses)
-                b1 = min(bs, b0 + _TAIL_MAX_BS)
-                k = b1 - b0
-                akey = (threading.get_ident(), k)           # ctypes releases the GIL during the call that reads them: per thread
-                arrs = _arr_cache.get(akey)
-                if arrs is None:
-                    arrs = _arr_cache[akey] = ((C.c_int64 * (k + 1))(), (C.c_float * (5 * k))())
-                doff, img5 = arrs
-                base = offs[b0]
-                doff[:] = [o - base for o in offs[b0:b1 + 1]] if base else offs[b0:b1 + 1]
-                flat = []
-                for j in range(b0, b1):
-                    shape, ratio_pad = shapes[j][0], shapes[j][1]
-                    flat += (ratio_pad[1][0], ratio_pad[1][1], ratio_pad[0][0], shape[1], shape[0])
-                img5[:] = flat
-                tgk, ntk = tg, nt
-                if nt and (b0 or b1 < bs):                       # a chunk of a very large batch: its labels, re-based
-                    sel = (tg[:, 0] >= b0) & (tg[:, 0] < b1)
-                    tgk = tg[sel].clone()
-                    tgk[:, 0] -= b0
-                    ntk = int(tgk.shape[0])
-                lo, hi = offs[b0], offs[b1]
-                if hi == lo:
-                    continue
-
-                def part(t, cols):
-                    return C.c_void_p(t.data_ptr() + lo * cols * 4)
-                if b1 < bs or b0:                                # not the last chunk of several: the rows are waited for at the end
+            for ch in tb.chunks(shapes):                         # (one call for any batch size val.py uses)
+                if tb.bs > MAX_BS:                               # a chunk of several: the flag is armed again for each
                     flag_np[0] = _lib._PENDING
                 rc = L.obb_val_tail_batch_polled_f32(
-                    part(packed, 7), C.cast(doff, C.c_void_p), k, C.c_void_p(tgk.data_ptr()) if ntk else null, ntk, tcols,
-                    C.cast(img5, C.c_void_p), C.c_void_p(iv.data_ptr()), niou,
-                    part(boxes[0], 10) if boxes else null, part(boxes[1], 6) if boxes else null,
-                    part(boxes[2], 10) if boxes else null, part(boxes[3], 6) if boxes else null,
-                    part(host, niou + 2), C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(st), C.c_void_p(flag.data_ptr()))
+                    ch.part(tb.packed, 7), ch.doff, ch.k, ch.tg_ptr, ch.ntk, ch.tcols, ch.img5, iv.data_ptr(), niou, *ch.box_parts(boxes),
+                    ch.part(host, niou + 2), ws.data_ptr(), ws.numel(), st, flag.data_ptr())
                 _lib.check(rc, "obb_val_tail_batch_f32")
                 _lib.wait_count(flag_np, dev)                    # every row of this chunk is in `host`
     # (the pinned buffer is reused by the next batch.  Copy and compare through numpy, single-threaded: a torch CPU op on these
     #  ~44k elements fans out to the whole intra-op pool -- 128 OpenMP workers on the GPU boxes -- whose spinning uses up the
     #  container's CPU quota: the kernel then parks the process for the rest of the 100 ms period, profiles/r5_host_stall.md)
-    arr = host.numpy().copy()
-    host = torch.from_numpy(arr)
-    correct = torch.from_numpy(arr[:, :niou] > 0.5).split(counts)
-    conf = host[:, niou].split(counts)
-    pcls = host[:, niou + 1].split(counts)
-    out = list(zip(correct, conf, pcls))
-    return (out, (boxes, offs)) if want_boxes else out
+    out = split_rows(host.numpy().copy(), niou, tb.counts)
+    return (out, (boxes, tb.offs)) if want_boxes else out
 
 
-def _obb_tail_launch(L, packed, offs, bs, tg, nt, tcols, iv, niou, rows, row0, match_label, match_iou, dev, st):
-    """obb_val_tail_batch_obb_f32 on a batch laid out for the HBB tail (chunks of _TAIL_MAX_BS images): the stats rows go to
-    rows[row0 + d], the match arrays to [d], d = the packed row of the detection."""
-    import ctypes as C
-    null = C.c_void_p(0)
-    for b0 in range(0, bs, _TAIL_MAX_BS):
-        b1 = min(bs, b0 + _TAIL_MAX_BS)
-        k = b1 - b0
-        lo, hi = offs[b0], offs[b1]
-        if hi == lo:
-            continue
-        doff = (C.c_int64 * (k + 1))(*[o - lo for o in offs[b0:b1 + 1]])
-        tgk, ntk, base = tg, nt, None
-        if nt and (b0 or b1 < bs):                               # a chunk of a very large batch: its labels, re-based
-            base = torch.nonzero((tg[:, 0] >= b0) & (tg[:, 0] < b1))[:, 0]
-            tgk = tg[base].clone()
-            tgk[:, 0] -= b0
-            ntk = int(tgk.shape[0])
+def _obb_tail_launch(L, tb, iv, niou, rows, row0, match_label, match_iou, st):
+    """obb_val_tail_batch_obb_f32 on every chunk of the batch: the stats rows go to rows[row0 + d], the match arrays to [d],
+    d = the packed row of the detection."""
+    for ch in tb.chunks():
         rc = L.obb_val_tail_batch_obb_f32(
-            C.c_void_p(packed.data_ptr() + lo * 28), null, C.cast(doff, C.c_void_p), k, C.c_void_p(tgk.data_ptr()) if ntk else null, ntk,
-            tcols, C.c_void_p(iv.data_ptr()), niou, C.c_void_p(rows.data_ptr() + (row0 + lo) * (niou + 2) * 4),
-            C.c_void_p(match_label.data_ptr() + lo * 4), C.c_void_p(match_iou.data_ptr() + lo * 4), C.c_void_p(st))
+            ch.part(tb.packed, 7), None, ch.doff, ch.k, ch.tg_ptr, ch.ntk, ch.tcols, iv.data_ptr(), niou,
+            ch.part(rows, niou + 2, row0), ch.part(match_label, 1), ch.part(match_iou, 1), st)
         _lib.check(rc, "obb_val_tail_batch_obb_f32")
-        if base is not None and ntk:                             # rows of the chunk's label list -> rows of `targets`
-            ml = match_label[lo:hi]
-            ml.copy_(torch.where(ml >= 0, base.to(torch.int32)[ml.clamp(min=0).long()], ml))
+        if ch.rows is not None and ch.ntk:                       # rows of the chunk's label list -> rows of `targets`
+            ml = match_label[ch.lo:ch.hi]
+            ml.copy_(torch.where(ml >= 0, ch.rows.to(torch.int32)[ml.clamp(min=0).long()], ml))
 
 
 def val_tail_batch_obb(preds, targets, iouv, return_match=False):
@@ -270,33 +174,23 @@ def val_tail_batch_obb(preds, targets, iouv, return_match=False):
     targets  (nt, >= 7) labels of the batch [img cls cx cy l s theta ...] in pixels of the letterboxed frame
     No shapes: both boxes stay in the letterboxed frame (the rotated IoU does not change under scale_polys).  With return_match
     also, per image, (match_label int32: the row of `targets` each detection kept or -1, match_iou float32) on the device."""
-    bs = len(preds)
-    if bs == 0:
+    if len(preds) == 0:
         return ([], []) if return_match else []
+    _lib.require_cuda(preds[0], "pred")
     dev = preds[0].device
-    if dev.type != "cuda":
-        _lib.require_cuda(preds[0], "pred")
-    counts = [p.shape[0] for p in preds]
-    offs = [0] * (bs + 1)
-    for b in range(bs):
-        offs[b + 1] = offs[b] + counts[b]
-    n = offs[bs]
-    niou = int(iouv.shape[0])
-    packed = _pack_dets(preds, dev, n)
-    tg = _as_f32_cuda(targets, dev) if targets.dim() == 2 and targets.shape[0] else None
-    nt, tcols = (tg.shape[0], tg.shape[1]) if tg is not None else (0, 0)
-    iv = _as_f32_cuda(iouv, dev)
+    tb = TailBatch(preds, targets, dev)
+    if not tb.in_place:
+        _lib.require_cuda_preds(preds)
+    n, niou = tb.n, int(iouv.shape[0])
+    iv = as_f32(iouv, dev)
     rows = torch.empty((n, niou + 2), dtype=torch.float32, device=dev)
     match_label = torch.full((n,), -1, dtype=torch.int32, device=dev)
     match_iou = torch.full((n,), -1.0, dtype=torch.float32, device=dev)
     if n:
         with _lib.guard(dev):
-            _obb_tail_launch(_lib.lib(), packed, offs, bs, tg, nt, tcols, iv, niou, rows, 0, match_label, match_iou, dev,
-                             _lib.stream_handle(dev))
-    arr = rows.cpu().numpy()
-    host = torch.from_numpy(arr)
-    out = list(zip(torch.from_numpy(arr[:, :niou] > 0.5).split(counts), host[:, niou].split(counts), host[:, niou + 1].split(counts)))
-    return (out, list(zip(match_label.split(counts), match_iou.split(counts)))) if return_match else out
+            _obb_tail_launch(_lib.lib(), tb, iv, niou, rows, 0, match_label, match_iou, _lib.stream_handle(dev))
+    out = split_rows(rows.cpu().numpy(), niou, tb.counts)
+    return (out, list(zip(match_label.split(tb.counts), match_iou.split(tb.counts)))) if return_match else out
 
 
 class ValStats:
@@ -314,11 +208,10 @@ class ValStats:
         self.n, self.m = 0, 0
         self._rows = torch.empty((max(1, int(capacity)), self.niou + 2), dtype=torch.float32, device=self.device)
         self._tcls = torch.empty(max(1, int(capacity) // 8), dtype=torch.float32, device=self.device)
-        self._result = None
+        self._result = [None, None]            # of _metrics(obb=False / True)
         # obb=True: the same rows with process_batch on the ROTATED boxes (obb_val_tail_batch_obb_f32), row for row beside the others
         self._rows_obb = torch.empty_like(self._rows) if self.obb else None
         self._match = None
-        self._result_obb = None
 
     @property
     def rows(self):
@@ -344,86 +237,55 @@ class ValStats:
         the packed device arrays (pred_poly, pred_hbb, pred_polyn, pred_hbbn) and the per-image offsets.
         confusion: a utils.metrics.ConfusionMatrix -- val.py:245-246 with plots=True: its launch runs right behind the tail's
         two, on the same packed detections and targets."""
-        import ctypes as C
         dev = self.device
-        bs = len(preds)
         if int(iouv.shape[0]) != self.niou:
             raise RuntimeError(f"ValStats: iouv has {int(iouv.shape[0])} levels, this accumulator {self.niou}")
-        offs = [0] * (bs + 1)
-        for b in range(bs):
-            if preds[b].device != dev:
-                _lib.require_cuda(preds[b], "pred")
-                raise RuntimeError(f"ValStats: pred on {preds[b].device}, the accumulator on {dev}")
-            offs[b + 1] = offs[b] + preds[b].shape[0]
-        n = offs[bs]
-        self._result = None
-        tg = _as_f32_cuda(targets, dev) if targets.dim() == 2 and targets.shape[0] else None
-        nt, tcols = (tg.shape[0], tg.shape[1]) if tg is not None else (0, 0)
+        for p in preds:
+            if p.device != dev:
+                _lib.require_cuda(p, "pred")
+                raise RuntimeError(f"ValStats: pred on {p.device}, the accumulator on {dev}")
+        tb = TailBatch(preds, targets, dev)
+        n, nt = tb.n, tb.nt
+        self._result = [None, None]
         if nt:
             self._tcls = self._grown(self._tcls, self.m, self.m + nt)
-            self._tcls[self.m:self.m + nt] = tg[:, 1]
+            self._tcls[self.m:self.m + nt] = tb.tg[:, 1]
             self.m += nt
-        boxes = None
-        if want_boxes:
-            boxes = (torch.empty((n, 10), dtype=torch.float32, device=dev), torch.empty((n, 6), dtype=torch.float32, device=dev),
-                     torch.empty((n, 10), dtype=torch.float32, device=dev), torch.empty((n, 6), dtype=torch.float32, device=dev))
+        boxes = box_arrays(n, dev) if want_boxes else None
         if n == 0:
-            return (boxes, offs) if want_boxes else None
-        packed = _pack_dets(preds, dev, n)
-        iv = _as_f32_cuda(iouv, dev)
+            return (boxes, tb.offs) if want_boxes else None
+        iv = as_f32(iouv, dev)
         self._rows = self._grown(self._rows, self.n, self.n + n)
         if self.obb:
             self._rows_obb = self._grown(self._rows_obb, self.n, self.n + n)
-            self._result_obb = None
-        cols = self.niou + 2
         L = _lib.lib()
-        null = C.c_void_p(0)
         with _lib.guard(dev):
             st = _lib.stream_handle(dev)
             ws = _lib.workspace(L.obb_val_tail_batch_workspace_bytes(n, nt), dev, st)
-            for b0 in range(0, bs, _TAIL_MAX_BS):
-                b1 = min(bs, b0 + _TAIL_MAX_BS)
-                k = b1 - b0
-                lo, hi = offs[b0], offs[b1]
-                if hi == lo:
-                    continue
-                doff = (C.c_int64 * (k + 1))(*[o - lo for o in offs[b0:b1 + 1]])
-                flat = []
-                for j in range(b0, b1):
-                    shape, ratio_pad = shapes[j][0], shapes[j][1]
-                    flat += (ratio_pad[1][0], ratio_pad[1][1], ratio_pad[0][0], shape[1], shape[0])
-                img5 = (C.c_float * (5 * k))(*flat)
-                tgk, ntk = tg, nt
-                if nt and (b0 or b1 < bs):                       # a chunk of a very large batch: its labels, re-based
-                    sel = (tg[:, 0] >= b0) & (tg[:, 0] < b1)
-                    tgk = tg[sel].clone()
-                    tgk[:, 0] -= b0
-                    ntk = int(tgk.shape[0])
-
-                def part(t, c, base=0):
-                    return C.c_void_p(t.data_ptr() + (base + lo) * c * 4)
+            for ch in tb.chunks(shapes):
                 rc = L.obb_val_tail_batch_f32(
-                    part(packed, 7), C.cast(doff, C.c_void_p), k, C.c_void_p(tgk.data_ptr()) if ntk else null, ntk, tcols,
-                    C.cast(img5, C.c_void_p), C.c_void_p(iv.data_ptr()), self.niou,
-                    part(boxes[0], 10) if boxes else null, part(boxes[1], 6) if boxes else null,
-                    part(boxes[2], 10) if boxes else null, part(boxes[3], 6) if boxes else null,
-                    part(self._rows, cols, self.n), C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(st))
+                    ch.part(tb.packed, 7), ch.doff, ch.k, ch.tg_ptr, ch.ntk, ch.tcols, ch.img5, iv.data_ptr(), self.niou,
+                    *ch.box_parts(boxes), ch.part(self._rows, self.niou + 2, self.n), ws.data_ptr(), ws.numel(), st)
                 _lib.check(rc, "obb_val_tail_batch_f32")
                 if confusion is not None:
-                    confusion._launch(L, part(packed, 7), C.cast(doff, C.c_void_p), k, hi - lo, C.c_void_p(tgk.data_ptr()) if ntk else null,
-                                      ntk, tcols, C.cast(img5, C.c_void_p), dev, st)
+                    confusion._launch(L, tb, ch, st)
             if self.obb:                                         # (the match arrays of the last batch stay readable: last_match)
                 self._match = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
-                _obb_tail_launch(L, packed, offs, bs, tg, nt, tcols, iv, self.niou, self._rows_obb, self.n, self._match[0], self._match[1],
-                                 dev, st)
+                _obb_tail_launch(L, tb, iv, self.niou, self._rows_obb, self.n, self._match[0], self._match[1], st)
         self.n += n
-        return (boxes, offs) if want_boxes else None
+        return (boxes, tb.offs) if want_boxes else None
 
-    def _metrics(self):
-        if self._result is None:
+    def _metrics(self, obb=False):
+        """(the 7-tuple of ap_per_class, info) over `rows`, or over `rows_obb`; kept until the next batch."""
+        rows = self.rows_obb if obb else self.rows
+        if self._result[obb] is None:
             from .utils import metrics
-            self._result = metrics.ap_from_rows(self.rows, self.target_cls, self.niou)
-        return self._result
+            self._result[obb] = metrics.ap_from_rows(rows, self.target_cls, self.niou)
+        return self._result[obb]
+
+    def _cpu(self, rows):
+        arr = rows.cpu().numpy()
+        return arr[:, :self.niou] > 0.5, arr[:, self.niou].copy(), arr[:, self.niou + 1].copy(), self.target_cls.cpu().numpy()
 
     def ap_per_class(self):
         """utils.metrics.ap_per_class over everything added so far (the 7-tuple of numpy arrays)."""
@@ -436,8 +298,7 @@ class ValStats:
 
     def cpu(self):
         """(correct bool (n, niou), conf (n), pcls (n), tcls (m)) numpy arrays: the four arrays of val.py:269."""
-        arr = self.rows.cpu().numpy()
-        return arr[:, :self.niou] > 0.5, arr[:, self.niou].copy(), arr[:, self.niou + 1].copy(), self.target_cls.cpu().numpy()
+        return self._cpu(self.rows)
 
     # ---- obb=True: the oriented-box statistics, accessor for accessor
     def _need_obb(self):
@@ -458,20 +319,12 @@ class ValStats:
 
     def ap_per_class_obb(self):
         """utils.metrics.ap_per_class over the oriented-box rows: the OBB mAP@0.5 and mAP@0.5:0.95 of everything added so far."""
-        return self._metrics_obb()[0]
-
-    def _metrics_obb(self):
-        self._need_obb()
-        if self._result_obb is None:
-            from .utils import metrics
-            self._result_obb = metrics.ap_from_rows(self.rows_obb, self.target_cls, self.niou)
-        return self._result_obb
+        return self._metrics(True)[0]
 
     @property
     def any_tp_obb(self):
-        return self._metrics_obb()[1][1] > 0
+        return self._metrics(True)[1][1] > 0
 
     def cpu_obb(self):
         """cpu() of the oriented-box rows."""
-        arr = self.rows_obb.cpu().numpy()
-        return arr[:, :self.niou] > 0.5, arr[:, self.niou].copy(), arr[:, self.niou + 1].copy(), self.target_cls.cpu().numpy()
+        return self._cpu(self.rows_obb)
