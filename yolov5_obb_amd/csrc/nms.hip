@@ -1122,6 +1122,16 @@ int obb_device_info(int* cu_count, int* wave_size, char* arch_name, int arch_nam
 
 }  // extern "C"
 
+#ifdef OBB_DECODE_TRACE
+// (development builds, tools/decode_trace.sh) the stamps of the last k_decode launch; the buffer is cleared
+extern "C" int obb_debug_decode_trace(unsigned long long* words) {
+  static unsigned long long zero[obb::kDecTraceWgs * 16];
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpyFromSymbol(words, HIP_SYMBOL(obb::g_decode_trace), sizeof(obb::g_decode_trace)) != hipSuccess) return -2;
+  return hipMemcpyToSymbol(HIP_SYMBOL(obb::g_decode_trace), zero, sizeof(obb::g_decode_trace)) == hipSuccess ? 0 : -3;
+}
+#endif
+
 #ifdef OBB_SMALL_TRACE
 // (development builds, tools/small_trace.sh) the stamps of the last k_nms_small launch; both buffers are cleared
 extern "C" int obb_debug_small_trace2(unsigned long long* words) {

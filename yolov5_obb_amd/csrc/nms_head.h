@@ -68,7 +68,9 @@ __global__ __launch_bounds__(kHeadThreads) void k_decode_head(DecodeArgs a, type
   __shared__ float s_obj[TP];
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (a.z_ticket != nullptr) {                                   // (kernel-uniform) the state of the later launches, as k_decode does
+  // (kernel-uniform) the state of the later launches, as k_decode does: only the blocks the call's path reads (nms_plan.h:
+  // zero_bar / zero_alive -- a block the path does not read comes with a count of 0)
+  if (a.z_ticket != nullptr) {
     const long long i = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * kHeadThreads + tid, n = (long long)gridDim.x * gridDim.y * kHeadThreads;
     if (i < a.n_ticket) a.z_ticket[i] = 0;
     for (long long k = i; k < a.n_bar16; k += n) a.z_bar16[k] = make_uint4(0u, 0u, 0u, 0u);

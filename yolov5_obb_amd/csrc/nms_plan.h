@@ -261,6 +261,10 @@ struct ObbPlan {
   int psrs;                  // the three-launch sort (psrs_sort.h) instead of the radix sort
   unsigned gparts;           // k_gather_out's parts per image (0: fused_out)
   int window;                // nms_window(max_det)
+  // State of the later launches that the call's first kernel zeroes (the filter kernel of a call with caller-kept counters, else
+  // k_reset_state).  Every call zeroes what ITS path reads, so a call never depends on what an earlier call of another path left:
+  int zero_bar;              // the persistent kernel's barrier block, which also holds the abort flag k_gather_out reads
+  int zero_alive;            // the alive bitmap k_sort_prep_lds ORs its bits into (the radix-sort path clears it itself)
 };
 
 static inline ObbPlan plan_nms_obb(const ObbPlanIn& in, const NmsEnv& env) {
@@ -326,6 +330,11 @@ static inline ObbPlan plan_nms_obb(const ObbPlanIn& in, const NmsEnv& env) {
   // parts per image: one up to ~2k expected candidates (the kept rows fit the kernel's LDS and 256 threads), then one per 1024
   if (!p.fused_out)
     p.gparts = p.expected_cand <= 2048 ? 1u : (unsigned)((p.expected_cand + 1023) / 1024 > 16 ? 16 : (p.expected_cand + 1023) / 1024);
+  // k_nms_small with its fused output stage reads neither the barrier block nor the abort flag; self-sorting segments build their
+  // alive words in LDS.  (A call that k_nms_small gives up on -- a segment too big -- is repeated by the caller with another hint:
+  // the repeat's own plan takes the persistent kernel and says zero_bar.)
+  p.zero_bar = (!p.small_nms || !p.fused_out) ? 1 : 0;
+  p.zero_alive = (p.lds_sort && !p.self_sort) ? 1 : 0;
   return p;
 }
 

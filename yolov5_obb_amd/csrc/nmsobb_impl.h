@@ -162,6 +162,29 @@ constexpr int kDecStage = 128;         // staged candidates per wave (LDS) befor
 // class groups of 16 are loaded on demand: nc > 32), and the box.  Everything a group needs is requested up front.
 constexpr int kDecCslRegs = 12;          // ceil(180 / 16)
 constexpr int kDecClsRegs = 2;           // class groups of 16 that travel with the row
+#ifdef OBB_DECODE_TRACE
+// (development builds, tools/decode_trace.sh) 16 words per workgroup of the last k_decode launch: 1, entry, after the first barrier,
+// objectness used by the first / the last wave, list built, rows reduced by the first / the last wave, slot atomic returned, exit
+// (wall_clock64 ticks of 10 ns), then n_rows and the candidates the workgroup staged.  The waves meet in LDS; thread 0 stores the record.
+constexpr int kDecTraceWgs = 2048;
+__device__ unsigned long long g_decode_trace[kDecTraceWgs * 16];
+#define DTRACE_DECL() __shared__ unsigned long long s_tr[16]; if (threadIdx.x < 16) s_tr[threadIdx.x] = (threadIdx.x == 3 || threadIdx.x == 6) ? ~0ull : 0ull; \
+  if (threadIdx.x == 0) s_tr[1] = wall_clock64()
+#define DTRACE_T0(slot) do { if (threadIdx.x == 0) s_tr[slot] = wall_clock64(); } while (0)
+#define DTRACE_WAVE(slot_min, slot_max) do { if ((threadIdx.x & 63) == 0) { const unsigned long long t_ = wall_clock64(); \
+  atomicMin(&s_tr[slot_min], t_); atomicMax(&s_tr[slot_max], t_); } } while (0)
+#define DTRACE_ADD(slot, v) do { if ((threadIdx.x & 63) == 0) atomicAdd(&s_tr[slot], (unsigned long long)(v)); } while (0)
+#define DTRACE_END(n_rows) do { DTRACE_WAVE(15, 9); __syncthreads(); \
+  const unsigned wg_ = blockIdx.y * gridDim.x + blockIdx.x; \
+  if (threadIdx.x < 16 && wg_ < (unsigned)kDecTraceWgs) g_decode_trace[wg_ * 16 + threadIdx.x] = threadIdx.x == 0 ? 1ull : threadIdx.x == 10 ? (unsigned long long)(n_rows) : s_tr[threadIdx.x]; } while (0)
+#else
+#define DTRACE_DECL() do {} while (0)
+#define DTRACE_T0(slot) do {} while (0)
+#define DTRACE_WAVE(slot_min, slot_max) do {} while (0)
+#define DTRACE_ADD(slot, v) do {} while (0)
+#define DTRACE_END(n_rows) do {} while (0)
+#endif
+
 template <typename T>
 struct DecQuad {
   float csl[kDecCslRegs];
@@ -172,6 +195,11 @@ struct DecQuad {
   bool valid;
 };
 
+// Every load of a row is UNCONDITIONAL: a lane that wants nothing reads element 0 of its row (of row 0 for a lane without a row), and
+// what it read is dropped where it would be USED (reduce_quad: the key of a bin >= 180 is 0, a class >= nc is not looked at), never by
+// a select on the loaded value here.  A load under `cond ? *p : x` -- and a select straight on a loaded value, which the compiler
+// turns back into such a branch -- is compiled with the wait for its result inside the branch: that made the 18 (and, in phase 1,
+// the 4) loads of a lane 18 dependent round trips (profiles/decode_trace_before.md).  Check the assembly after touching this.
 template <typename T>
 __device__ __forceinline__ DecQuad<T> dec_load_quad(const T* img, int no, int nc, const uint32_t* s_row, const float* s_obj,
                                                     int j, int n_rows, int l16) {
@@ -179,20 +207,14 @@ __device__ __forceinline__ DecQuad<T> dec_load_quad(const T* img, int no, int nc
   r.valid = j < n_rows;
   r.row = r.valid ? s_row[j] : 0u;
   r.obj = r.valid ? s_obj[j] : 0.f;
-  const T* base = img + (size_t)r.row * no;
+  const T* base = img + (size_t)r.row * (uint32_t)no;
   const T* csl = base + 5 + nc;
 #pragma unroll
-  for (int k = 0; k < kDecCslRegs; k++) {
-    const int bin = k * 16 + l16;
-    r.csl[k] = (r.valid && bin < 180) ? ld_as_float<T>(csl + bin) : -__builtin_inff();
-  }
+  for (int k = 0; k < kDecCslRegs; k++) r.csl[k] = ld_as_float<T>((k * 16 + l16 < 180) ? csl + k * 16 + l16 : base);
 #pragma unroll
-  for (int g = 0; g < kDecClsRegs; g++) {
-    const int c = g * 16 + l16;
-    r.cls[g] = (r.valid && c < nc) ? ld_as_float<T>(base + 5 + c) : 0.f;
-  }
+  for (int g = 0; g < kDecClsRegs; g++) r.cls[g] = ld_as_float<T>((g * 16 + l16 < nc) ? base + 5 + g * 16 + l16 : base);
 #pragma unroll
-  for (int k = 0; k < 4; k++) r.box[k] = r.valid ? ld_as_float<T>(base + k) : 0.f;
+  for (int k = 0; k < 4; k++) r.box[k] = ld_as_float<T>(base + k);
   return r;
 }
 
@@ -222,13 +244,7 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
   int staged = 0;   // wave-uniform
   int flags_seen = 0;
   if (tid == 0) s_n = 0;
-  if (a.z_ticket != nullptr) {                                   // (kernel-uniform) what k_reset_state zeroes for the sort and NMS launches
-    const long long i = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * kDecThreads + tid, n = (long long)gridDim.x * gridDim.y * kDecThreads;
-    if (i < a.n_ticket) a.z_ticket[i] = 0;
-    for (long long k = i; k < a.n_bar16; k += n) a.z_bar16[k] = make_uint4(0u, 0u, 0u, 0u);
-    for (long long k = i; k < a.n_alive16; k += n) a.z_alive16[k] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  __syncthreads();
+  DTRACE_DECL();
 
   auto write_out = [&](long long base, int count) {
     for (int i = lane; i < count; i += 64) {
@@ -257,13 +273,25 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
   // times (0 / 14 / 44 rows: min / median / max on the planted-object batch); the objectness reads do not care (a strided
   // read is one line per row anyway, the dense column is read in 32-byte pieces).
   auto row_of = [&](int q) -> long long { return ((long long)(q * (kDecThreads / 16) + (tid >> 4)) * gridDim.x + blockIdx.x) * 16 + (tid & 15); };
+  // (unconditional loads, all kDecMaxG in flight before the first is used: a lane without a row -- q >= G, or behind the image's
+  // last row -- reads the image's last row, and the value is not looked at)
+  const T* ocol = a.objcol ? (const T*)a.objcol + (size_t)b * a.A : img + 4;          // 128 bytes per wave : one line per row
+  const long long ostride = a.objcol ? 1 : a.no;
 #pragma unroll
   for (int q = 0; q < kDecMaxG; q++) {
     const long long row = row_of(q);
-    obj[q] = (q >= G || row >= a.A) ? 0.f
-             : a.objcol ? ld_as_float<T>((const T*)a.objcol + (size_t)b * a.A + row)       // 128 bytes per wave
-                        : ld_as_float<T>(img + (size_t)row * a.no + 4);                     // one line per row
+    obj[q] = ld_as_float<T>(ocol + (size_t)(row < a.A ? row : a.A - 1) * ostride);
   }
+  // The state of the later launches that the call's plan wants zeroed (kernel-uniform: what k_reset_state zeroes for a call without
+  // caller-kept counters).  Nothing in this kernel reads it: the stores go out behind the objectness loads and are not waited for.
+  if (a.z_ticket != nullptr) {
+    const long long i = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * kDecThreads + tid, n = (long long)gridDim.x * gridDim.y * kDecThreads;
+    if (i < a.n_ticket) a.z_ticket[i] = 0;
+    for (long long k = i; k < a.n_bar16; k += n) a.z_bar16[k] = make_uint4(0u, 0u, 0u, 0u);
+    for (long long k = i; k < a.n_alive16; k += n) a.z_alive16[k] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  __syncthreads();                                               // (s_n = 0 before the first wave counts its rows)
+  DTRACE_T0(2);
 #pragma unroll
   for (int q = 0; q < kDecMaxG; q++) {
     const bool p = q < G && row_of(q) < a.A && obj[q] > thr;
@@ -279,38 +307,56 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
       }
     }
   }
+  DTRACE_WAVE(3, 4);
   __syncthreads();
+  DTRACE_T0(5);
   const int n_rows = s_n;
 
   // ---- phase 2: the listed rows in groups of four (one per 16-lane row); wave wv takes groups wv, wv + 8, ...,
   // kDecDepth groups requested before the first is reduced
   const int l16 = lane & 15, sub = lane >> 4;
   const int ncg = (a.nc + 15) >> 4;
-  auto reduce_quad = [&](const DecQuad<T>& cur) {
-    // CSL decode: first arg-max over the 180 bins (:822-823), inside the 16-lane row
+  // what every candidate of a row shares
+  struct RowOut { float bx, by, bl, bs_, theta; int bflags; long long rw; };
+  auto stage = [&](const RowOut& o, bool p, float conf, int c) {        // one candidate per lane with p set
+    const unsigned long long pb = __ballot(p);
+    const int np = __popcll(pb);
+    if (np == 0) return;
+    if (staged + np > kDecStage) flush_wave();
+    if (p) {
+      const int i = staged + __popcll(pb & lanemask_lt());
+      c0s[i] = make_float4(o.bx, o.by, o.bl, o.bs_);
+      c1s[i] = make_float4(o.theta, conf, (float)c, 0.f);
+      kys[i] = ((unsigned long long)score_desc_key(conf) << 32) | (unsigned long long)(uint32_t)(o.rw * a.nc + c);
+      flags_seen |= o.bflags;
+    }
+    staged += np;
+    DTRACE_ADD(11, np);
+  };
+  auto row_out = [&](float bx, float by, float bl, float bs_, unsigned long long tk, uint32_t row) {
+    float tv; int ti;
+    argmax_unkey(row_max_u64(tk), tv, ti);     // CSL decode: first arg-max over the 180 bins (:822-823), inside the 16-lane row
+    RowOut o;
+    o.bx = bx; o.by = by; o.bl = bl; o.bs_ = bs_;
+    o.theta = ((float)(ti - 90) / 180.0f) * 3.141592f;
+    o.bflags = cand_flags(bx, bl, bs_, a.win_lo, a.win_hi);
+    o.rw = (long long)row;
+    return o;
+  };
+  // :830 best class of the row (a NaN maximum fails bv > thr: the row is dropped), :831, :835
+  auto stage_best = [&](const RowOut& o, bool valid, unsigned long long bestk) {
+    float bv; int bi;
+    argmax_unkey(row_max_u64(bestk), bv, bi);
+    stage(o, valid && l16 == 0 && bv > thr && class_allowed(a.cm, bi), bv, bi);
+  };
+  auto reduce_quad = [&](const DecQuad<T>& cur) __attribute__((always_inline)) {
     unsigned long long tk = argmax_key(cur.csl[0], l16);
 #pragma unroll
-    for (int k = 1; k < kDecCslRegs; k++) { const unsigned long long kk = argmax_key(cur.csl[k], k * 16 + l16); tk = kk > tk ? kk : tk; }
-    float tv; int ti;
-    argmax_unkey(row_max_u64(tk), tv, ti);
-    const float theta = ((float)(ti - 90) / 180.0f) * 3.141592f;
-    const float bx = cur.box[0], by = cur.box[1], bl = cur.box[2], bs_ = cur.box[3];
-    const int bflags = cand_flags(bx, bl, bs_, a.win_lo, a.win_hi);
-    const long long rw = (long long)cur.row;
-    auto stage = [&](bool p, float conf, int c) {        // one candidate per lane with p set
-      const unsigned long long pb = __ballot(p);
-      const int np = __popcll(pb);
-      if (np == 0) return;
-      if (staged + np > kDecStage) flush_wave();
-      if (p) {
-        const int i = staged + __popcll(pb & lanemask_lt());
-        c0s[i] = make_float4(bx, by, bl, bs_);
-        c1s[i] = make_float4(theta, conf, (float)c, 0.f);
-        kys[i] = ((unsigned long long)score_desc_key(conf) << 32) | (unsigned long long)(uint32_t)(rw * a.nc + c);
-        flags_seen |= bflags;
-      }
-      staged += np;
-    };
+    for (int k = 1; k < kDecCslRegs; k++) {             // (key 0, below the key of every value, for what a lane read in place of a bin >= 180)
+      const unsigned long long kk = (k * 16 + l16 < 180) ? argmax_key(cur.csl[k], k * 16 + l16) : 0ull;
+      tk = kk > tk ? kk : tk;
+    }
+    const RowOut o = row_out(cur.box[0], cur.box[1], cur.box[2], cur.box[3], tk, cur.row);
     // class confidences (:820 conf = obj * cls in the input dtype)
     unsigned long long bestk = argmax_key(-__builtin_inff(), 0x7fffffff);
     for (int g = 0; g < ncg; g++) {
@@ -319,14 +365,10 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
       if (g < kDecClsRegs) raw = (g == 0) ? cur.cls[0] : cur.cls[1];
       else raw = (cur.valid && c < a.nc) ? ld_as_float<T>(img + (size_t)cur.row * a.no + 5 + c) : 0.f;
       const float v = (cur.valid && c < a.nc) ? mul_in_dtype<T>(raw, cur.obj) : -__builtin_inff();
-      if (a.multi_label) stage(cur.valid && c < a.nc && v > thr && class_allowed(a.cm, c), v, c);             // :827, :835
+      if (a.multi_label) stage(o, cur.valid && c < a.nc && v > thr && class_allowed(a.cm, c), v, c);             // :827, :835
       else if (c < a.nc) { const unsigned long long kk = argmax_key(v, c); bestk = kk > bestk ? kk : bestk; }   // a NaN wins
     }
-    if (!a.multi_label) {
-      float bv; int bi;
-      argmax_unkey(row_max_u64(bestk), bv, bi);                         // :830 (a NaN maximum fails bv > thr: the row is dropped)
-      stage(cur.valid && l16 == 0 && bv > thr && class_allowed(a.cm, bi), bv, bi);                            // :831, :835
-    }
+    if (!a.multi_label) stage_best(o, cur.valid, bestk);
   };
   static_assert(kDecClsRegs == 2, "reduce_quad selects cls[0] / cls[1] explicitly");
   for (int g0 = wv; g0 * 4 < n_rows; g0 += kDecWaves * kDecDepth) {
@@ -347,6 +389,7 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
     const int fl = (__ballot(flags_seen & kImgSmall) ? kImgSmall : 0) | (__ballot(flags_seen & kImgWide) ? kImgWide : 0);
     if (fl && lane == 0) atomicOr(&a.tiny[b], fl);
   }
+  DTRACE_WAVE(6, 7);
   // ---- one atomic per workgroup for whatever is still staged
   if (lane == 0) s_cnt[wv] = staged;
   __syncthreads();
@@ -356,9 +399,11 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
     s_base = tot ? atomicAdd(&a.cnt[b * kCntPad], tot) : 0;
   }
   __syncthreads();
+  DTRACE_T0(8);
   int base = s_base;
   for (int w = 0; w < wv; w++) base += s_cnt[w];
   write_out(base, staged);
+  DTRACE_END(n_rows);
 }
 
 // apriori label rows (utils/general.py:807-813), prepared by the host layer as [img, x, y, l, s, theta, conf, cls]
@@ -1433,15 +1478,16 @@ static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t 
   {
     Carve& nv0 = cv.nms;
     // (cap_img is a multiple of 64 -> bs * cap_img / 64 words; + the guard words, rounded up to 16 bytes)
-    const long long alive16 = plan.lds_sort ? (long long)((((size_t)bs * cap_img) >> 6) + 8 + 1) / 2 : 0ll;
+    // only what the planned path reads (plan.zero_bar / zero_alive): the headline's self-sorting segments need neither block
+    const long long alive16 = plan.zero_alive ? (long long)((((size_t)bs * cap_img) >> 6) + 8 + 1) / 2 : 0ll;
+    const long long bar16 = plan.zero_bar ? (long long)(nv0.bar_bytes / 16) : 0ll;
     if (kept) {                                                    // the filter kernel zeroes what the later launches need
       d.z_ticket = cv.ticket; d.n_ticket = (int)(16 + bs + 1);
-      d.z_bar16 = reinterpret_cast<uint4*>(nv0.bar); d.n_bar16 = (long long)(nv0.bar_bytes / 16);
-      d.z_alive16 = reinterpret_cast<uint4*>(nv0.alive); d.n_alive16 = alive16;
+      d.z_bar16 = bar16 ? reinterpret_cast<uint4*>(nv0.bar) : nullptr; d.n_bar16 = bar16;
+      d.z_alive16 = alive16 ? reinterpret_cast<uint4*>(nv0.alive) : nullptr; d.n_alive16 = alive16;
     } else {
       k_reset_state<<<256, 256, 0, st>>>(cv.cnt, (int)(bs * kCntPad), cv.tiny, (int)bs, status, cv.ticket, (int)(16 + bs + 1),
-                                         reinterpret_cast<uint4*>(nv0.bar), (long long)(nv0.bar_bytes / 16),
-                                         reinterpret_cast<uint4*>(nv0.alive), alive16);
+                                         reinterpret_cast<uint4*>(nv0.bar), bar16, reinterpret_cast<uint4*>(nv0.alive), alive16);
     }
   }
   d.rows_per_thread = plan.rows_per_thread;
