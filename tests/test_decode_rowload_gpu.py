@@ -36,8 +36,9 @@ def _cmp(got, ref, what):
         assert g.shape == r.shape and torch.equal(g.cpu(), r), (what, "image", b, tuple(g.shape), tuple(r.shape))
 
 
-def _run(dev, pred_dev, ref_multi, ref_best, what, nc, expect_small=True):
-    """Both label modes, with and without the objectness column; the third call of a shape runs on the hints of the second."""
+def _run(dev, pred_dev, ref_multi, ref_best, what, nc, expect_small=True, kw=KW):
+    """Both label modes, with and without the objectness column; the third call of a shape runs on the hints of the second.
+    kw: the thresholds and max_det the references were made with."""
     from yolov5_obb_amd import _lib
     from yolov5_obb_amd.utils import general
     L = _lib.lib()
@@ -51,7 +52,7 @@ def _run(dev, pred_dev, ref_multi, ref_best, what, nc, expect_small=True):
             for rep in range(3):
                 L.obb_profile_enable(1)
                 try:
-                    got = general.non_max_suppression_obb(p, multi_label=multi, **KW)
+                    got = general.non_max_suppression_obb(p, multi_label=multi, **kw)
                 finally:
                     cnt = _stage_counts(L)
                     L.obb_profile_enable(0)
@@ -59,7 +60,7 @@ def _run(dev, pred_dev, ref_multi, ref_best, what, nc, expect_small=True):
             if nc > 1 and expect_small:
                 # the small-segment kernel (the shape's hint says which kernel the third call took); its segments sort themselves, with
                 # no sort launch in front, when every class can have a full segment of the image's candidate slots (csrc/nms_plan.h)
-                seg = general.hint_get(dev, A, nc, multi and nc > 1, KW["conf_thres"])["seg"]
+                seg = general.hint_get(dev, A, nc, multi and nc > 1, kw["conf_thres"])["seg"]
                 slots = -(-(A * (nc if multi else 1)) // 64) * 64
                 assert 0 < seg <= general._SEG_SMALL and cnt[0] > 0, (what, multi, col, seg, cnt)
                 assert (cnt[1] == 0) == (nc * general._SEG_SMALL <= slots), (what, multi, col, slots, cnt)
