@@ -5,7 +5,7 @@ word `row * nc + class` of a candidate key needs its fourth byte.
 
 The tensors are large in bytes and almost entirely zero: a zero row fails `obj > conf_thres`, so the oracle
 (oracle/pyref.py: non_max_suppression_obb) drops it in its first step and the comparison costs what the planted rows cost.
-What is planted is chosen from the kernel's row map (csrc/nmsobb_impl.h: k_decode, row_of), restated here as wg_rows:
+What is planted is chosen from the kernel's row map (csrc/nmsobb_front.h: k_decode, row_of), restated here as wg_rows:
 
     row = ((q * 32 + (tid >> 4)) * nwg + w) * 16 + (tid & 15),   nwg = ceil(A / (512 G)),   q < G,   row < A
 

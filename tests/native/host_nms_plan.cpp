@@ -77,6 +77,13 @@ extern "C" void np_help_place(void* base, int helpers, int64_t nseg, int64_t n_p
 }
 extern "C" int np_nms_grid(int64_t nseg, int64_t n_slots, int cap_first, int cus) { return obb::nms_grid(nseg, n_slots, cap_first, cus); }
 extern "C" int np_nms_window(int64_t max_keep) { return obb::nms_window(max_keep); }
+// the class filter's bits: out5 = w[0..3], all
+extern "C" void np_class_mask(const int32_t* classes, int n_classes, uint64_t* out5) {
+  unsigned long long w[4]; int all = -1;
+  obb::class_mask_fill(classes, n_classes, w, &all);
+  for (int i = 0; i < 4; i++) out5[i] = w[i];
+  out5[4] = (uint64_t)(int64_t)all;
+}
 
 #ifdef NMS_PLAN_MAIN
 // Every decision on a grid of values around its thresholds (the hand-written cases of the test lie on it), every parser on the
@@ -112,6 +119,14 @@ int main() {
       np_obb(in16, packed && nc == 7 ? -0.5f : 0.45f, 4096.f, e, o20);
       for (int64_t x : o20) sum += x;
     }
+  {
+    const int32_t ids[] = {-1, 0, 63, 64, 127, 128, 255, 256, 1000, 63};
+    uint64_t m5[5];
+    np_class_mask(ids, (int)(sizeof ids / sizeof *ids), m5);
+    if (m5[0] != ((1ull << 63) | 1ull) || m5[1] != ((1ull << 63) | 1ull) || m5[2] != 1ull || m5[3] != (1ull << 63) || m5[4] != 0) { printf("class mask is wrong\n"); return 1; }
+    np_class_mask(nullptr, 3, m5);
+    if (m5[4] != 1 || (m5[0] | m5[1] | m5[2] | m5[3])) { printf("class mask (no list) is wrong\n"); return 1; }
+  }
   const int helpers = 5; const int64_t nseg = 33, n_pos = 1000;
   const uint64_t need = np_help_bytes(helpers, nseg, n_pos);
   unsigned char* base = (unsigned char*)aligned_alloc(256, need);

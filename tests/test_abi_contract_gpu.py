@@ -5,7 +5,7 @@ The three runs must give the oracle's result, bit for bit the same.  The same wo
 be refused with OBB_ERR_WORKSPACE before anything is written.  One size per entry runs again under obb_nms_set_max_grid(8)
 (query and call sized from the same value) and on a side stream behind a delay (every launch, memset and copy on `stream`).
 
-The sizes are the edges of the workspace carves (csrc/nms.hip: carve, csrc/nmsobb_impl.h: obb_carve): the grid block at
+The sizes are the edges of the workspace carves (csrc/nms_driver.h: carve, csrc/nmsobb_impl.h: obb_carve): the grid block at
 n = 8192, both implementations at n = 16384, grid_slots at 32768, cap_max(nseg) at nseg = 1 | 64 | 65, more segments than
 teams, and the helper scratch of the small-segment kernel that aliases the edge lists.
 

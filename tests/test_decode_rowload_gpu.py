@@ -1,4 +1,4 @@
-"""GPU: the row reads of the filter kernel (csrc/nmsobb_impl.h: k_decode, dec_load_quad) against oracle/pyref.py, bit for bit and in
+"""GPU: the row reads of the filter kernel (csrc/nmsobb_front.h: k_decode, dec_load_quad) against oracle/pyref.py, bit for bit and in
 the same order.  Every load of a row is unconditional -- a lane that wants nothing reads an element of its row and drops it -- so
 the cases are the ones where "which element, of which row" can go wrong: a partial 16-row chunk, one row short of and one over a
 chunk, a row count that is no multiple of a workgroup's rows, more than one workgroup; rows that start on odd element offsets

@@ -1,4 +1,4 @@
-"""GPU: the filter kernel (csrc/nmsobb_impl.h: k_decode) at two and four rows per thread, and the sorts behind it on tie words that
+"""GPU: the filter kernel (csrc/nmsobb_front.h: k_decode) at two and four rows per thread, and the sorts behind it on tie words that
 need their fourth byte, against oracle/pyref.py -- bit for bit and in the same order (torch.equal per image, no tolerance).
 
 The host plan (csrc/nms_plan.h: plan_nms_obb) picks the rows per thread G from bs * A: 1 below 491,520 rows, 2 below 983,040,

@@ -1,7 +1,7 @@
 """Bounded runs of the random differential checks (tools/self_fuzz.py: the fused non_max_suppression_obb on random shapes, self-sorting
 segments against the sort-kernel path and against the oracle restatement of utils/general.py:772-862; tools/nms_fuzz.py: the single-list
 NMS entry points against the C oracle).  The long runs of round 6 (2,240 + 470 + 580 cases) found one difference in the product -- label
-rows passed the class filter, fixed in csrc/nmsobb_impl.h: k_append_extra -- and one that no CPU oracle can pin (float64 IoU of exact
+rows passed the class filter, fixed in csrc/nmsobb_front.h: k_append_extra -- and one that no CPU oracle can pin (float64 IoU of exact
 duplicates against thr = 1.0: the last bit of the platform's double sin / cos)."""
 import os
 import subprocess

@@ -2,7 +2,7 @@
 
   * nms_pairs (csrc/nms_core.h): item t of the upper triangle of nb x nb tiles -> (row tile, column tile) through a float
     square root estimate that is fixed up with the exact row offsets;
-  * k_decode (csrc/nmsobb_impl.h): 16-row chunks dealt round-robin to the workgroups of an image -- every row of the image
+  * k_decode (csrc/nmsobb_front.h): 16-row chunks dealt round-robin to the workgroups of an image -- every row of the image
     must be read by exactly one (workgroup, thread, q), for every G the host picks.
 A mistake in either would not crash: it would silently skip or repeat work."""
 import numpy as np

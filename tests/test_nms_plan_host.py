@@ -230,6 +230,7 @@ def lib(tmp_path_factory):
     L.np_help_place.argtypes, L.np_help_place.restype = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_uint64)], None
     L.np_nms_grid.argtypes, L.np_nms_grid.restype = [C.c_int64, C.c_int64, C.c_int, C.c_int], C.c_int
     L.np_nms_window.argtypes, L.np_nms_window.restype = [C.c_int64], C.c_int
+    L.np_class_mask.argtypes, L.np_class_mask.restype = [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint64)], None
     return L
 
 
@@ -561,6 +562,53 @@ def test_launch_geometry(lib):
     for mk in (-1, 0, 1, 300, 2047, 2048, 2049, 100000, 1 << 28, (1 << 28) + 1, 1 << 40):
         assert lib.np_nms_window(mk) == ref_nms_window(mk)
     assert lib.np_nms_window(300) == 8192 and lib.np_nms_window(1 << 40) == 1 << 30
+
+
+# ---- the class filter's bits (class_mask_fill): the fill as it stood inline in run_nms_obb
+def ref_class_mask(classes, n):
+    """-> (w[0..3], all).  classes None: a NULL pointer; n: the count the caller states."""
+    w = [0, 0, 0, 0]
+    for c in (classes or [])[:max(n, 0)]:
+        if 0 <= c < 256:
+            w[c >> 6] |= 1 << (c & 63)
+    return w, int(classes is None or n <= 0)
+
+
+def lib_class_mask(L, classes, n):
+    out = (C.c_uint64 * 5)(*([0xdeadbeefdeadbeef] * 5))               # (every word is written)
+    arr = (C.c_int32 * max(len(classes), 1))(*classes) if classes is not None else None
+    L.np_class_mask(arr, n, out)
+    return list(out[:4]), int(C.c_int64(out[4]).value)
+
+
+CLASS_MASKS = {
+    "NULL": (None, 3),
+    "NULL, n = 0": (None, 0),
+    "n = 0": ([5, 6], 0),
+    "n < 0": ([5, 6], -1),
+    "ids outside 0..255 are ignored": ([-1, 256, 1000], 3),
+    "the edges of every word": ([0, 63, 64, 127, 128, 255], 6),
+    "a repeated id": ([17, 17, 200, 17], 4),
+    "only the first n ids": ([1, 2, 3, 4], 2),
+    "ignored ids among valid ones": ([-1, 0, 256, 255, 1000, 64], 6),
+}
+
+
+@pytest.mark.parametrize("name", list(CLASS_MASKS))
+def test_class_mask(lib, name):
+    classes, n = CLASS_MASKS[name]
+    assert lib_class_mask(lib, classes, n) == ref_class_mask(classes, n)
+
+
+def test_class_mask_expected_values(lib):
+    assert lib_class_mask(lib, *CLASS_MASKS["NULL"]) == ([0, 0, 0, 0], 1)
+    assert lib_class_mask(lib, *CLASS_MASKS["n = 0"]) == ([0, 0, 0, 0], 1)
+    assert lib_class_mask(lib, *CLASS_MASKS["ids outside 0..255 are ignored"]) == ([0, 0, 0, 0], 0), "a filter that allows nothing"
+    assert lib_class_mask(lib, *CLASS_MASKS["the edges of every word"]) == ([1 | 1 << 63, 1 | 1 << 63, 1, 1 << 63], 0), "exactly their bits"
+    assert lib_class_mask(lib, *CLASS_MASKS["a repeated id"]) == ([1 << 17, 0, 0, 1 << (200 - 192)], 0)
+    for c in range(256):                                                # one id, one bit
+        w, all_ = lib_class_mask(lib, [c], 1)
+        assert all_ == 0 and sum(bin(x).count("1") for x in w) == 1 and (w[c >> 6] >> (c & 63)) & 1
 
 
 STRINGS = [None, "", "0", "1", "2", "3", "-1", "999", "x", "1x", " 2", "01", "10", "300", str(MK_PEND1), str(MK_PEND1 - 1)]

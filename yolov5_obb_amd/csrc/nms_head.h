@@ -1,4 +1,4 @@
-// Front kernel of obb_non_max_suppression_obb_head (included by nms.hip after nmsobb_impl.h, namespace obb).
+// Front kernel of obb_non_max_suppression_obb_head (namespace obb; built on nmsobb_front.h, launched by the driver of nmsobb_impl.h).
 //
 // k_decode_head does the work of k_decode -- confidence filter, conf = obj * cls, multi-label expansion or best class, CSL
 // arg-max, class filter, candidate records and sort keys -- but reads the Detect head's 1x1-conv outputs (bs, na*no, ny, nx)
@@ -22,7 +22,17 @@
 // entry starts at in torch.cat(_clip_augmented(y), 1), so keys, tie order and kept list are those of obb_detect_decode_tta followed
 // by the eager NMS.  Everything under `if constexpr (TTA)` is compiled into that instantiation only.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
+#include <stdint.h>
+
 #include "detect_math.h"
+#include "dtype_device.h"
+#include "launch_once.h"
+#include "nms_driver.h"
+#include "nmsobb_front.h"
+#include "obb_device.h"
+#include "obb_hip.h"
 #include "tta_head_plan.h"
 
 namespace obb {
@@ -276,27 +286,53 @@ __global__ __launch_bounds__(kHeadThreads) void k_decode_head(DecodeArgs a, type
   write_out(base, staged);
 }
 
+// The table of obb_non_max_suppression_obb_head from the caller's level arrays, with the limits of obb_detect_decode_levels and
+// obb_non_max_suppression_obb checked on the way; *A_out: the rows of z the levels make up
+static int head_front_build(int nl, const void* const* conv_out, int dtype, int64_t bs, int64_t na, int64_t no, const int64_t* ny,
+                            const int64_t* nx, const float* anchors_px_host, const float* strides_host, HeadFront* h_out, int64_t* A_out) {
+  HeadFront& h = *h_out;
+  const int64_t nc = no - 5 - 180;
+  if (nl < 1 || nl > kHeadMaxLevels || !conv_out || !ny || !nx || !anchors_px_host || !strides_host || bs < 1 || na < 1 ||
+      na > OBB_LOSS_MAX_ANCHORS || nc < 1 || nc > 256 || !dtype_known(dtype) || bs * na > 65535)
+    return OBB_ERR_BAD_ARG;
+  const size_t esz = dtype_size(dtype);
+  const int TP = 256 / (int)esz;                                  // kHeadTile<T> of the dtype's element type
+  h.nl = nl; h.na = (int)na; h.vec = 1;
+  int64_t A = 0, tiles = 0;
+  for (int l = 0; l < kHeadMaxLevels; l++) {
+    if (l >= nl) { h.in[l] = nullptr; h.ny[l] = h.nx[l] = 0; h.a_off[l] = A; h.tile_end[l] = (int)tiles; h.stride[l] = 0.f; continue; }
+    if (!conv_out[l] || ny[l] < 1 || nx[l] < 1 || ny[l] * nx[l] * na * no > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
+    const int64_t HW = ny[l] * nx[l];
+    h.in[l] = conv_out[l]; h.ny[l] = (int)ny[l]; h.nx[l] = (int)nx[l]; h.a_off[l] = A; h.stride[l] = strides_host[l];
+    for (int a = 0; a < OBB_LOSS_MAX_ANCHORS; a++) {
+      h.anchor_px[l][a][0] = a < na ? anchors_px_host[((size_t)l * na + a) * 2] : 0.f;
+      h.anchor_px[l][a][1] = a < na ? anchors_px_host[((size_t)l * na + a) * 2 + 1] : 0.f;
+    }
+    if ((((uintptr_t)conv_out[l]) & 15) != 0 || ((size_t)HW * esz) % 16 != 0) h.vec = 0;
+    tiles += (HW + TP - 1) / TP;
+    if (tiles > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
+    h.tile_end[l] = (int)tiles;
+    A += na * HW;
+  }
+  *A_out = A;
+  return OBB_OK;
+}
+
 static size_t head_lds_bytes(int64_t no) { return (size_t)no * kHeadPitchDw * 4; }
 
-// the launch run_nms_obb makes in place of k_decode (grid: the levels' tiles x bs*na)
+// the launch run_nms_obb makes in place of k_decode (grid: the levels' tiles x bs*na); dev: current_device() as the call read it
 template <bool TTA>
-static int launch_decode_head_of(const typename HeadFrontOf<TTA>::type& h, const DecodeArgs& d, int dtype, hipStream_t st) {
+static int launch_decode_head_of(const typename HeadFrontOf<TTA>::type& h, const DecodeArgs& d, int dtype, int dev, hipStream_t st) {
   static OncePerDevice attr;
-  if (const int attr_dev = attr.need(); attr_dev != OncePerDevice::kDone) {
-    const int lds = (int)head_lds_bytes(5 + 256 + 180);
-    if (hipFuncSetAttribute((const void*)k_decode_head<float, TTA>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_decode_head<__half, TTA>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_decode_head<bf16_t, TTA>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return OBB_ERR_LAUNCH;
-    attr.mark(attr_dev);
-  }
+  if (!raise_lds_once_on(dev, attr, head_lds_bytes(5 + 256 + 180), k_decode_head<float, TTA>, k_decode_head<__half, TTA>, k_decode_head<bf16_t, TTA>))
+    return OBB_ERR_LAUNCH;
   const dim3 grid((unsigned)h.tile_end[h.nl - 1], (unsigned)(d.bs * h.na));
   const size_t lds = head_lds_bytes(d.no);
   OBB_DISPATCH_DTYPE(dtype, T, k_decode_head<T, TTA><<<grid, kHeadThreads, lds, st>>>(d, h));
   return OBB_OK;
 }
-static int launch_decode_head(const HeadFront& h, const DecodeArgs& d, int dtype, hipStream_t st) { return launch_decode_head_of<false>(h, d, dtype, st); }
+static int launch_decode_head(const HeadFront& h, const DecodeArgs& d, int dtype, int dev, hipStream_t st) { return launch_decode_head_of<false>(h, d, dtype, dev, st); }
 // ... over the (pass, level) entries of augmented inference
-static int launch_decode_head_tta(const HeadFrontTta& h, const DecodeArgs& d, int dtype, hipStream_t st) { return launch_decode_head_of<true>(h, d, dtype, st); }
+static int launch_decode_head_tta(const HeadFrontTta& h, const DecodeArgs& d, int dtype, int dev, hipStream_t st) { return launch_decode_head_of<true>(h, d, dtype, dev, st); }
 
 }  // namespace obb

@@ -7,7 +7,7 @@
 
 namespace obb {
 
-// ---- persistent kernel (nms.hip, nms_core.h)
+// ---- persistent kernel (nms_driver.h, nms_core.h)
 // Chunk capacities: the first chunk has 2048 boxes, later chunks double up to 8192 for a single list, 2048 per segment for
 // batches of up to 64 segments and 1024 beyond.  (The edge list of a team is sized for the worst case cap*(cap-1)/2 of one
 // chunk: 134 MB at 8192, 8.4 MB at 2048, 2 MB at 1024 -- times the number of teams.)
@@ -26,7 +26,7 @@ constexpr int kSmallMax = OBB_NMS_SMALL_SEG;        // boxes per segment (includ
 constexpr int kSmallWords = kSmallMax / 64;         // bit-matrix words per row
 constexpr int kSmallHelpMax = 256;
 
-// ---- fused driver (nmsobb_impl.h, psrs_sort.h)
+// ---- fused driver (nmsobb_impl.h, nmsobb_front.h, psrs_sort.h)
 constexpr int64_t kSortLdsHint = OBB_NMS_SORT_LDS_HINT;   // use the in-LDS path when the previous call's largest image was at most this
 constexpr int kPsMaxN = 131072;       // kPsRun * kPsMaxRuns (psrs_sort.h asserts it)
 constexpr int kDecThreads = 512;      // 8 waves: a workgroup whose share of rows is three times the median still needs one pass

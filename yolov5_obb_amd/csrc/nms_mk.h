@@ -55,7 +55,7 @@ struct MkCtl {                            // control block of a call (zeroed bef
   int bail;                               // the phase kernels stand back (pending / edge list overflow, too many brute boxes): the persistent kernel behind them carries on
   int n1;                                 // pending pairs of the phase in flight: undecided after the quick tests
   int ticket;                             // workgroups of a decide kernel that are through (the last one runs the serial phase behind it)
-  // the data as a whole (nms.hip: local_extras' per-workgroup partials, reduced by the first select): the bounding box of the finite
+  // the data as a whole (nms_single.h: local_extras' per-workgroup partials, reduced by the first select): the bounding box of the finite
   // centres and the radius limit of every table -- rcap = min(largest, 4 x mean) inflated circumradius.  Fixed per call: a table
   // build has no statistics pass of its own.
   float dx0, dy0, dxr, dyr, drcap, dmag; int pad;
@@ -283,7 +283,7 @@ __device__ void mk_build_table(const MkArgs& a, const float4* __restrict__ rec, 
 static_assert(kMkCapMax == 2 * kMkTile, "mk_build_table holds a chunk as two tiles");
 static_assert(kMkSlots / kMkThreads == 16, "the slot starts are written as two 16-byte stores per thread");
 
-// The data as a whole from the key kernel's per-workgroup partials (nms.hip: local_extras): bounding box of the finite centres,
+// The data as a whole from the key kernel's per-workgroup partials (nms_single.h: local_extras): bounding box of the finite centres,
 // (xr^2 + yr^2) * 1.001 (+inf when there is no usable extent: then every box is brute and the call goes to the persistent kernel),
 // and the radius limit min(largest, 4 x mean) of the inflated circumradius 0.5005 * sqrt(w^2 + h^2) (riou_device.h).
 __device__ __forceinline__ MkData mk_data_stats(const int* __restrict__ bbpart, int nparts, int* s_redi) {

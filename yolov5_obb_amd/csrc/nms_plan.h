@@ -1,4 +1,4 @@
-// nms_plan.h -- which path a call of the NMS drivers takes, as plain host code.  run_nms (nms.hip) and run_nms_obb (nmsobb_impl.h)
+// nms_plan.h -- which path a call of the NMS drivers takes, as plain host code.  run_nms (nms_single.h) and run_nms_obb (nmsobb_impl.h)
 // take a snapshot of what the decision depends on, ask plan_single_list / plan_nms_obb, and launch what the plan says: every `if`
 // of a driver that chooses a path reads a field of a plan.  Pure functions of their arguments (the one reader of the environment,
 // nms_env, aside): no HIP, no allocation, no global state; tests/test_nms_plan_host.py drives them without a GPU.
@@ -228,6 +228,18 @@ static inline size_t small_help_bytes(int helpers, int64_t nseg, int64_t n_pos) 
   return w.total();
 }
 
+// The caller's class filter (utils/general.py:835) as the bits of ClassMask (nmsobb_front.h): bit c & 63 of w[c >> 6] for every
+// listed class id in 0 .. 255; ids outside that range are ignored (nc <= 256: no candidate carries them), a repeated id sets its
+// bit once.  NULL or n_classes <= 0: no filter (*all = 1, no bit set).
+static inline void class_mask_fill(const int32_t* classes_host, int n_classes, unsigned long long w[4], int* all) {
+  *all = (classes_host == nullptr || n_classes <= 0) ? 1 : 0;
+  for (int i = 0; i < 4; i++) w[i] = 0ull;
+  for (int i = 0; i < n_classes && classes_host; i++) {
+    const int c = classes_host[i];
+    if (c >= 0 && c < 256) w[c >> 6] |= 1ull << (c & 63);
+  }
+}
+
 struct ObbPlanIn {
   int64_t bs, A;
   int nc, agnostic, multi_label;
@@ -237,7 +249,7 @@ struct ObbPlanIn {
   int64_t max_nms, max_det;
   int64_t expected_cand;     // the caller's word, all 64 bits
   int out_packed;
-  int hw_cus, cus;           // hw_cu_count(), cu_count() (capped by obb_nms_set_max_grid)
+  int hw_cus, cus;           // the current device's, as the call read them once (nms_driver.h: DeviceCus; cus is capped by obb_nms_set_max_grid)
   long long ecap;            // of the nested NMS carve
   size_t sort_tmp_bytes;     // of the nested NMS carve ...
   size_t ps_scratch_bytes;   // ... and what the three-launch sort needs of it

@@ -1,5 +1,5 @@
-// Greedy NMS of MANY SMALL segments, one workgroup per segment, nothing shared between workgroups -- gfx950 (included by
-// nms.hip behind nms_core.h, namespace obb).
+// Greedy NMS of MANY SMALL segments, one workgroup per segment, nothing shared between workgroups -- gfx950 (namespace
+// obb; the fused driver of nmsobb_impl.h launches it).
 //
 // The regime: the fused driver at the reference's default thresholds (utils/general.py:772-862 with conf 0.25): 16 images x
 // 16 classes = 256 segments of ~100 boxes (a few above 200).  The persistent kernel of nms_core.h is built for lists of 10^5
@@ -23,7 +23,13 @@
 // flag and is left alone: the host layer repeats the call on the persistent kernel (it chooses this kernel from the
 // previous call's largest segment, include/obb_hip.h: expected_cand).
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "geom.h"
+#include "nms_core.h"
 #include "nms_limits.h"
+#include "obb_device.h"
 
 namespace obb {
 

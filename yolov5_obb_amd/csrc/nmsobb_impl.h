@@ -1,4 +1,5 @@
-// Fused non_max_suppression_obb for gfx950 (included by nms.hip, namespace obb).
+// Fused non_max_suppression_obb for gfx950 (namespace obb): the kernels behind the front and the driver.  The front kernels are
+// in nmsobb_front.h (k_decode) and nms_head.h (the conv-layout fronts), which this header includes; the C entries are in nms.hip.
 //
 // Replaces the per-image Python loop of utils/general.py:772-862 (>= 10 tiny ATen kernels and >= 3 host
 // syncs per image, then obb_nms with a device->host mask copy) by ONE stream-ordered call for the whole batch:
@@ -27,404 +28,26 @@
 //
 // The only host<->device traffic is the caller reading the bs counts (+ the overflow word) afterwards.
 #pragma once
-#include "dtype_device.h"
-#include "obb_device.h"
-#include "segsort.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "geom.h"
+#include "launch_once.h"
+#include "nms_core.h"
+#include "nms_driver.h"
+#include "nms_head.h"
+#include "nms_limits.h"
 #include "nms_plan.h"
+#include "nms_small.h"
+#include "nmsobb_front.h"
+#include "obb_device.h"
+#include "obb_hip.h"
+#include "psrs_sort.h"
+#include "segsort.h"
+#include "tta_head_plan.h"
+#include "ws_layout.h"
 
 namespace obb {
-
-struct ClassMask { unsigned long long w[4]; int all; };   // allowed classes (nc <= 256), all != 0: no filter
-
-// product rounded to the tensor dtype: x[:, 5:ci] *= x[:, 4:5] happens in the input dtype (utils/general.py:820)
-template <typename T> __device__ __forceinline__ float mul_in_dtype(float a, float b);
-template <> __device__ __forceinline__ float mul_in_dtype<float>(float a, float b) { return a * b; }
-template <> __device__ __forceinline__ float mul_in_dtype<__half>(float a, float b) { return __half2float(__float2half_rn(a * b)); }
-// (bf16: two 8-bit significands give a 16-bit product, exact in fp32, so the one rounding below is torch's bf16 multiply bit for bit)
-template <> __device__ __forceinline__ float mul_in_dtype<bf16_t>(float a, float b) { return round_to_dtype<bf16_t>(a * b); }
-// python float threshold compared against a tensor of the input dtype: the scalar is cast to that dtype
-template <typename T> __device__ __forceinline__ float thr_in_dtype(float t);
-template <> __device__ __forceinline__ float thr_in_dtype<float>(float t) { return t; }
-template <> __device__ __forceinline__ float thr_in_dtype<__half>(float t) { return __half2float(__float2half_rn(t)); }
-template <> __device__ __forceinline__ float thr_in_dtype<bf16_t>(float t) { return round_to_dtype<bf16_t>(t); }
-
-// wave arg-max with "first maximum" tie rule (torch.max over a dimension: utils/general.py:822, :830).  Value and index
-// travel as ONE 64-bit key -- order-preserving image of the float in the high word (-0 counts as +0; every NaN, of either
-// sign and any payload, maps to the one key 0xFFFFFFFF above +inf: torch.max / torch.argmax rank a NaN as the maximum and
-// take the first of several), ~index in the low word -- so the reduction is a plain unsigned max: four DPP steps inside the
-// 16-lane rows (quad swaps, half-row and row mirrors: a few cycles each, where ds_bpermute costs an LDS round trip per
-// step), then the four row results meet through v_readlane.
-__device__ __forceinline__ unsigned long long argmax_key(float v, int i) {
-  const uint32_t b = __float_as_uint(v + 0.0f);
-  const uint32_t m = (v != v) ? 0xFFFFFFFFu : (b & 0x80000000u) ? ~b : (b | 0x80000000u);   // (unkeyed: a NaN)
-  return ((unsigned long long)m << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
-}
-template <int CTRL>
-__device__ __forceinline__ unsigned long long dpp_max_u64(unsigned long long k) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)k, CTRL, 0xF, 0xF, true);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(k >> 32), CTRL, 0xF, 0xF, true);
-  const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-  return o > k ? o : k;
-}
-__device__ __forceinline__ unsigned long long row_max_u64(unsigned long long k) {    // all 64 lanes active
-  k = dpp_max_u64<0xB1>(k);      // quad_perm [1,0,3,2]
-  k = dpp_max_u64<0x4E>(k);      // quad_perm [2,3,0,1]
-  k = dpp_max_u64<0x141>(k);     // row_half_mirror
-  return dpp_max_u64<0x140>(k);  // row_mirror: every lane holds the max of its 16-lane row
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {   // all 64 lanes active
-  k = row_max_u64(k);
-  unsigned long long r[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++)
-    r[j] = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(k >> 32), j * 16) << 32) |
-           (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)k, j * 16);
-  const unsigned long long a = r[0] > r[1] ? r[0] : r[1], b = r[2] > r[3] ? r[2] : r[3];
-  return a > b ? a : b;
-}
-__device__ __forceinline__ void argmax_unkey(unsigned long long k, float& v, int& i) {
-  const uint32_t m = (uint32_t)(k >> 32);
-  v = __uint_as_float((m & 0x80000000u) ? (m ^ 0x80000000u) : ~m);
-  i = (int)(0xFFFFFFFFu - (uint32_t)k);
-}
-__device__ __forceinline__ void wave_argmax_first(float& v, int& i) {
-  argmax_unkey(wave_max_u64(argmax_key(v, i)), v, i);
-}
-
-struct DecodeArgs {
-  const void* pred;          // [bs][A][no]
-  const void* objcol;        // [bs][A] = pred[..., 4] stored densely by the producer (obb_detect_decode_col), or null
-  long long A;
-  int no, nc, bs;
-  float conf_thres;
-  int multi_label;
-  int rows_per_thread;       // G: a workgroup of k_decode covers kDecThreads * G rows
-  ClassMask cm;
-  long long cap_img;         // candidate slots per image
-  float4* cand;              // [bs*cap_img][2]: {x,y,l,s} {theta,conf,cls,0}
-  unsigned long long* keys;  // [bs*cap_img]
-  uint32_t* vals;            // [bs*cap_img] slot index inside the image region
-  int* cnt;                  // [bs * kCntPad] candidates produced (may exceed cap_img: overflow), one 256-B line each
-  int* tiny;                 // [bs] flags of the image (kImg*): what decides whether its classes may run as independent NMS segments
-  float win_lo, win_hi;      // every candidate's circle must lie in win_lo < x < win_hi (a window narrower than max_wh), else kImgWide
-  // state of the LATER launches that this kernel zeroes on its way (a call with caller-kept counters has no reset launch:
-  // obb_non_max_suppression_obb_st); all NULL / 0: k_reset_state did it
-  int* z_ticket; int n_ticket;
-  uint4* z_bar16; long long n_bar16;
-  uint4* z_alive16; long long n_alive16;
-};
-
-// Per-image flags (DecodeArgs::tiny).  The reference runs ONE list per image with xy += cls * max_wh (utils/general.py:849-851);
-// one NMS segment per class gives the same kept set exactly when no pair of boxes of DIFFERENT classes can interact:
-//   kImgSmall   a candidate has a short side in [0.001, 1) px: the reference's fp32 corner arithmetic is ill conditioned for such a
-//               box against a partner tens of thousands of pixels away (riou_device.h: rbox_pair_well_conditioned) and can
-//               report an overlap there.  Such an image keeps its class segments only if k_tiny_cross has CHECKED every
-//               ill-conditioned cross-class pair with the exact clip and found no IoU > thr (round 5; rounds 1-4: single list);
-//   kImgWide    a candidate's circle leaves the window [win_lo, win_hi] on x (an oversized or far-out box, NaN / inf): circles
-//               of different classes could really touch -- always the single list;
-//   kImgChecked k_tiny_cross ran for the image and completed its list of small boxes;   kImgCross  it found a cross-class hit.
-constexpr int kImgSmall = 1, kImgWide = 2, kImgChecked = 4, kImgCross = 8;
-__host__ __device__ __forceinline__ bool img_single_list(int t) {
-  return (t & kImgWide) || ((t & kImgSmall) && (!(t & kImgChecked) || (t & kImgCross)));
-}
-__device__ __forceinline__ int cand_flags(float x, float l, float s, float win_lo, float win_hi) {
-  const float mn = min_nan(l, s);
-  const float rr = sqrtf(l * l + s * s) * 0.501f + 0.5f;
-  int f = (mn >= 0.001f && mn < 1.0f) ? kImgSmall : 0;
-  if (!(x - rr > win_lo && x + rr < win_hi)) f |= kImgWide;     // (NaN / inf anywhere: the comparisons fail)
-  return f;
-}
-
-__device__ __forceinline__ bool class_allowed(const ClassMask& cm, int c) {
-  const int q = (c >> 6) & 3;   // select chain instead of a dynamic index: the mask lives in kernel-argument SGPRs
-  const unsigned long long w = q == 0 ? cm.w[0] : q == 1 ? cm.w[1] : q == 2 ? cm.w[2] : cm.w[3];
-  return cm.all || ((w >> (c & 63)) & 1ull);
-}
-
-// Candidate counters are padded to one 256-byte line each: same-word device atomics retire at ~11 ns apiece
-// (MI355X_MICROARCH.md "fanin"/"dequeue"), and 16 counters packed in one line would share one L2 channel.
-constexpr int kCntPad = 64;   // ints
-
-// Rows of a workgroup = kDecThreads * G (G = 1, 2 or 4 rows per thread, chosen by the host so that small batches still fill the
-// chip).  History: with one wave per 64 consecutive rows that also processed ITS passing rows one after the other, the
-// kernel took 52 us on a warm and 78-91 us on a freshly written configs[1] tensor -- even with the dense objectness column:
-// detector output is clustered (an object fires on neighbouring cells), so a few waves carried long serial chains of cold
-// row reads while most had none.  Now the workgroup compacts its passing rows into LDS and its four waves take them
-// round-robin, kDecDepth rows in flight per wave.
-constexpr int kDecWaves = kDecThreads / 64;
-constexpr int kDecMaxG = 4;
-constexpr int kDecDepth = 2;          // groups of four rows in flight per wave
-constexpr int kDecStage = 128;         // staged candidates per wave (LDS) before a flush
-
-// Phase 2 of k_decode works on FOUR rows per wave, one per 16-lane DPP row: a row of the head output holds ~200 elements,
-// and with a whole wave per row most of every instruction was bookkeeping (measured: ~450 wave instructions per row,
-// VALU-bound).  Lane l16 of a group holds angle bins l16, l16+16, ... (12 registers), classes l16 and 16+l16 (further
-// class groups of 16 are loaded on demand: nc > 32), and the box.  Everything a group needs is requested up front.
-constexpr int kDecCslRegs = 12;          // ceil(180 / 16)
-constexpr int kDecClsRegs = 2;           // class groups of 16 that travel with the row
-#ifdef OBB_DECODE_TRACE
-// (development builds, tools/decode_trace.sh) 16 words per workgroup of the last k_decode launch: 1, entry, after the first barrier,
-// objectness used by the first / the last wave, list built, rows reduced by the first / the last wave, slot atomic returned, exit
-// (wall_clock64 ticks of 10 ns), then n_rows and the candidates the workgroup staged.  The waves meet in LDS; thread 0 stores the record.
-constexpr int kDecTraceWgs = 2048;
-__device__ unsigned long long g_decode_trace[kDecTraceWgs * 16];
-#define DTRACE_DECL() __shared__ unsigned long long s_tr[16]; if (threadIdx.x < 16) s_tr[threadIdx.x] = (threadIdx.x == 3 || threadIdx.x == 6) ? ~0ull : 0ull; \
-  if (threadIdx.x == 0) s_tr[1] = wall_clock64()
-#define DTRACE_T0(slot) do { if (threadIdx.x == 0) s_tr[slot] = wall_clock64(); } while (0)
-#define DTRACE_WAVE(slot_min, slot_max) do { if ((threadIdx.x & 63) == 0) { const unsigned long long t_ = wall_clock64(); \
-  atomicMin(&s_tr[slot_min], t_); atomicMax(&s_tr[slot_max], t_); } } while (0)
-#define DTRACE_ADD(slot, v) do { if ((threadIdx.x & 63) == 0) atomicAdd(&s_tr[slot], (unsigned long long)(v)); } while (0)
-#define DTRACE_END(n_rows) do { DTRACE_WAVE(15, 9); __syncthreads(); \
-  const unsigned wg_ = blockIdx.y * gridDim.x + blockIdx.x; \
-  if (threadIdx.x < 16 && wg_ < (unsigned)kDecTraceWgs) g_decode_trace[wg_ * 16 + threadIdx.x] = threadIdx.x == 0 ? 1ull : threadIdx.x == 10 ? (unsigned long long)(n_rows) : s_tr[threadIdx.x]; } while (0)
-#else
-#define DTRACE_DECL() do {} while (0)
-#define DTRACE_T0(slot) do {} while (0)
-#define DTRACE_WAVE(slot_min, slot_max) do {} while (0)
-#define DTRACE_ADD(slot, v) do {} while (0)
-#define DTRACE_END(n_rows) do {} while (0)
-#endif
-
-template <typename T>
-struct DecQuad {
-  float csl[kDecCslRegs];
-  float cls[kDecClsRegs];
-  float box[4];
-  float obj;
-  uint32_t row;
-  bool valid;
-};
-
-// Every load of a row is UNCONDITIONAL: a lane that wants nothing reads element 0 of its row (of row 0 for a lane without a row), and
-// what it read is dropped where it would be USED (reduce_quad: the key of a bin >= 180 is 0, a class >= nc is not looked at), never by
-// a select on the loaded value here.  A load under `cond ? *p : x` -- and a select straight on a loaded value, which the compiler
-// turns back into such a branch -- is compiled with the wait for its result inside the branch: that made the 18 (and, in phase 1,
-// the 4) loads of a lane 18 dependent round trips (profiles/decode_trace_before.md).  Check the assembly after touching this.
-template <typename T>
-__device__ __forceinline__ DecQuad<T> dec_load_quad(const T* img, int no, int nc, const uint32_t* s_row, const float* s_obj,
-                                                    int j, int n_rows, int l16) {
-  DecQuad<T> r;
-  r.valid = j < n_rows;
-  r.row = r.valid ? s_row[j] : 0u;
-  r.obj = r.valid ? s_obj[j] : 0.f;
-  const T* base = img + (size_t)r.row * (uint32_t)no;
-  const T* csl = base + 5 + nc;
-#pragma unroll
-  for (int k = 0; k < kDecCslRegs; k++) r.csl[k] = ld_as_float<T>((k * 16 + l16 < 180) ? csl + k * 16 + l16 : base);
-#pragma unroll
-  for (int g = 0; g < kDecClsRegs; g++) r.cls[g] = ld_as_float<T>((g * 16 + l16 < nc) ? base + 5 + g * 16 + l16 : base);
-#pragma unroll
-  for (int k = 0; k < 4; k++) r.box[k] = ld_as_float<T>(base + k);
-  return r;
-}
-
-// k_decode: workgroup = 512 threads x G rows.  Phase 1 reads the objectness of every row -- from the dense column when the
-// producer stored one (obb_detect_decode_col), else one 2-4 byte element of each 400-800 byte row -- and compacts the rows
-// with obj > conf into an LDS list (wave ballot + one LDS atomic per wave).  Phase 2: the four waves take the listed rows
-// round-robin in groups of four (DecQuad above), kDecDepth groups in flight per wave, and stage the candidates in LDS.  Slots in the image's candidate region are claimed with ONE atomic per workgroup (plus
-// one per wave whenever its 128-entry stage fills up) and the staged records are written out coalesced.
-template <typename T>
-__global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
-  __shared__ float4 s_c0[kDecWaves][kDecStage], s_c1[kDecWaves][kDecStage];
-  __shared__ unsigned long long s_key[kDecWaves][kDecStage];
-  __shared__ int s_cnt[kDecWaves], s_base, s_n;
-  __shared__ uint32_t s_row[kDecThreads * kDecMaxG];
-  __shared__ float s_obj[kDecThreads * kDecMaxG];
-
-  const T* pred = (const T*)a.pred;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int b = blockIdx.y;
-  const int G = a.rows_per_thread;
-  const float thr = thr_in_dtype<T>(a.conf_thres);
-  const T* img = pred + (size_t)b * a.A * a.no;
-  float4* cand = a.cand + (size_t)b * a.cap_img * 2;
-  unsigned long long* keys = a.keys + (size_t)b * a.cap_img;
-  uint32_t* vals = a.vals + (size_t)b * a.cap_img;
-  float4* c0s = s_c0[wv]; float4* c1s = s_c1[wv]; unsigned long long* kys = s_key[wv];
-  int staged = 0;   // wave-uniform
-  int flags_seen = 0;
-  if (tid == 0) s_n = 0;
-  DTRACE_DECL();
-
-  auto write_out = [&](long long base, int count) {
-    for (int i = lane; i < count; i += 64) {
-      const long long slot = base + i;
-      if (slot < a.cap_img) {
-        cand[slot * 2] = c0s[i];
-        cand[slot * 2 + 1] = c1s[i];
-        keys[slot] = kys[i];
-        vals[slot] = (uint32_t)slot;
-      }
-    }
-  };
-  auto flush_wave = [&]() {   // mid-kernel flush of a full stage: one atomic for the wave
-    int base = 0;
-    if (lane == 0) base = atomicAdd(&a.cnt[b * kCntPad], staged);
-    base = __shfl(base, 0);
-    write_out(base, staged);
-    staged = 0;
-  };
-
-  // ---- phase 1: objectness of the workgroup's rows                    :785  xc = prediction[..., 4] > conf_thres
-  float obj[kDecMaxG];
-  // 16-row chunks are dealt to the workgroups of the image round-robin (chunk c -> workgroup c % gridDim.x): detector output
-  // is clustered -- a coarse level holds hundreds of passing rows in a few thousand consecutive rows.  Contiguous 1024-row
-  // blocks left a handful of workgroups with ten times the average number of rows to reduce, 64-row chunks still three
-  // times (0 / 14 / 44 rows: min / median / max on the planted-object batch); the objectness reads do not care (a strided
-  // read is one line per row anyway, the dense column is read in 32-byte pieces).
-  auto row_of = [&](int q) -> long long { return ((long long)(q * (kDecThreads / 16) + (tid >> 4)) * gridDim.x + blockIdx.x) * 16 + (tid & 15); };
-  // (unconditional loads, all kDecMaxG in flight before the first is used: a lane without a row -- q >= G, or behind the image's
-  // last row -- reads the image's last row, and the value is not looked at)
-  const T* ocol = a.objcol ? (const T*)a.objcol + (size_t)b * a.A : img + 4;          // 128 bytes per wave : one line per row
-  const long long ostride = a.objcol ? 1 : a.no;
-#pragma unroll
-  for (int q = 0; q < kDecMaxG; q++) {
-    const long long row = row_of(q);
-    obj[q] = ld_as_float<T>(ocol + (size_t)(row < a.A ? row : a.A - 1) * ostride);
-  }
-  // The state of the later launches that the call's plan wants zeroed (kernel-uniform: what k_reset_state zeroes for a call without
-  // caller-kept counters).  Nothing in this kernel reads it: the stores go out behind the objectness loads and are not waited for.
-  if (a.z_ticket != nullptr) {
-    const long long i = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * kDecThreads + tid, n = (long long)gridDim.x * gridDim.y * kDecThreads;
-    if (i < a.n_ticket) a.z_ticket[i] = 0;
-    for (long long k = i; k < a.n_bar16; k += n) a.z_bar16[k] = make_uint4(0u, 0u, 0u, 0u);
-    for (long long k = i; k < a.n_alive16; k += n) a.z_alive16[k] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  __syncthreads();                                               // (s_n = 0 before the first wave counts its rows)
-  DTRACE_T0(2);
-#pragma unroll
-  for (int q = 0; q < kDecMaxG; q++) {
-    const bool p = q < G && row_of(q) < a.A && obj[q] > thr;
-    const unsigned long long mk = __ballot(p);
-    if (mk) {
-      int base = 0;
-      if (lane == 0) base = atomicAdd(&s_n, __popcll(mk));
-      base = __shfl(base, 0);
-      if (p) {
-        const int i = base + __popcll(mk & lanemask_lt());
-        s_row[i] = (uint32_t)row_of(q);
-        s_obj[i] = obj[q];
-      }
-    }
-  }
-  DTRACE_WAVE(3, 4);
-  __syncthreads();
-  DTRACE_T0(5);
-  const int n_rows = s_n;
-
-  // ---- phase 2: the listed rows in groups of four (one per 16-lane row); wave wv takes groups wv, wv + 8, ...,
-  // kDecDepth groups requested before the first is reduced
-  const int l16 = lane & 15, sub = lane >> 4;
-  const int ncg = (a.nc + 15) >> 4;
-  // what every candidate of a row shares
-  struct RowOut { float bx, by, bl, bs_, theta; int bflags; long long rw; };
-  auto stage = [&](const RowOut& o, bool p, float conf, int c) {        // one candidate per lane with p set
-    const unsigned long long pb = __ballot(p);
-    const int np = __popcll(pb);
-    if (np == 0) return;
-    if (staged + np > kDecStage) flush_wave();
-    if (p) {
-      const int i = staged + __popcll(pb & lanemask_lt());
-      c0s[i] = make_float4(o.bx, o.by, o.bl, o.bs_);
-      c1s[i] = make_float4(o.theta, conf, (float)c, 0.f);
-      kys[i] = ((unsigned long long)score_desc_key(conf) << 32) | (unsigned long long)(uint32_t)(o.rw * a.nc + c);
-      flags_seen |= o.bflags;
-    }
-    staged += np;
-    DTRACE_ADD(11, np);
-  };
-  auto row_out = [&](float bx, float by, float bl, float bs_, unsigned long long tk, uint32_t row) {
-    float tv; int ti;
-    argmax_unkey(row_max_u64(tk), tv, ti);     // CSL decode: first arg-max over the 180 bins (:822-823), inside the 16-lane row
-    RowOut o;
-    o.bx = bx; o.by = by; o.bl = bl; o.bs_ = bs_;
-    o.theta = ((float)(ti - 90) / 180.0f) * 3.141592f;
-    o.bflags = cand_flags(bx, bl, bs_, a.win_lo, a.win_hi);
-    o.rw = (long long)row;
-    return o;
-  };
-  // :830 best class of the row (a NaN maximum fails bv > thr: the row is dropped), :831, :835
-  auto stage_best = [&](const RowOut& o, bool valid, unsigned long long bestk) {
-    float bv; int bi;
-    argmax_unkey(row_max_u64(bestk), bv, bi);
-    stage(o, valid && l16 == 0 && bv > thr && class_allowed(a.cm, bi), bv, bi);
-  };
-  auto reduce_quad = [&](const DecQuad<T>& cur) __attribute__((always_inline)) {
-    unsigned long long tk = argmax_key(cur.csl[0], l16);
-#pragma unroll
-    for (int k = 1; k < kDecCslRegs; k++) {             // (key 0, below the key of every value, for what a lane read in place of a bin >= 180)
-      const unsigned long long kk = (k * 16 + l16 < 180) ? argmax_key(cur.csl[k], k * 16 + l16) : 0ull;
-      tk = kk > tk ? kk : tk;
-    }
-    const RowOut o = row_out(cur.box[0], cur.box[1], cur.box[2], cur.box[3], tk, cur.row);
-    // class confidences (:820 conf = obj * cls in the input dtype)
-    unsigned long long bestk = argmax_key(-__builtin_inff(), 0x7fffffff);
-    for (int g = 0; g < ncg; g++) {
-      const int c = g * 16 + l16;
-      float raw;
-      if (g < kDecClsRegs) raw = (g == 0) ? cur.cls[0] : cur.cls[1];
-      else raw = (cur.valid && c < a.nc) ? ld_as_float<T>(img + (size_t)cur.row * a.no + 5 + c) : 0.f;
-      const float v = (cur.valid && c < a.nc) ? mul_in_dtype<T>(raw, cur.obj) : -__builtin_inff();
-      if (a.multi_label) stage(o, cur.valid && c < a.nc && v > thr && class_allowed(a.cm, c), v, c);             // :827, :835
-      else if (c < a.nc) { const unsigned long long kk = argmax_key(v, c); bestk = kk > bestk ? kk : bestk; }   // a NaN wins
-    }
-    if (!a.multi_label) stage_best(o, cur.valid, bestk);
-  };
-  static_assert(kDecClsRegs == 2, "reduce_quad selects cls[0] / cls[1] explicitly");
-  for (int g0 = wv; g0 * 4 < n_rows; g0 += kDecWaves * kDecDepth) {
-    DecQuad<T> quads[kDecDepth];
-#pragma unroll
-    for (int i = 0; i < kDecDepth; i++) {
-      const int g = g0 + kDecWaves * i;
-      if (g * 4 < n_rows) quads[i] = dec_load_quad<T>(img, a.no, a.nc, s_row, s_obj, g * 4 + sub, n_rows, l16);
-    }
-#pragma unroll
-    for (int i = 0; i < kDecDepth; i++) {
-      const int g = g0 + kDecWaves * i;
-      if (g * 4 < n_rows) reduce_quad(quads[i]);
-    }
-  }
-
-  {
-    const int fl = (__ballot(flags_seen & kImgSmall) ? kImgSmall : 0) | (__ballot(flags_seen & kImgWide) ? kImgWide : 0);
-    if (fl && lane == 0) atomicOr(&a.tiny[b], fl);
-  }
-  DTRACE_WAVE(6, 7);
-  // ---- one atomic per workgroup for whatever is still staged
-  if (lane == 0) s_cnt[wv] = staged;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int w = 0; w < kDecWaves; w++) tot += s_cnt[w];
-    s_base = tot ? atomicAdd(&a.cnt[b * kCntPad], tot) : 0;
-  }
-  __syncthreads();
-  DTRACE_T0(8);
-  int base = s_base;
-  for (int w = 0; w < wv; w++) base += s_cnt[w];
-  write_out(base, staged);
-  DTRACE_END(n_rows);
-}
-
-// apriori label rows (utils/general.py:807-813), prepared by the host layer as [img, x, y, l, s, theta, conf, cls]
-__global__ void k_append_extra(const float* __restrict__ extra8, int m, long long A, int nc, DecodeArgs a) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  const float* e = extra8 + (size_t)i * 8;
-  const int b = (int)e[0];
-  if (b < 0 || b >= a.bs) return;
-  // a label row is a candidate like any other (:807-813 append it in front of the filters): conf = 1 > conf_thres (:827 / :831) and
-  // the class filter (:835) apply to it -- until round 6 the class filter did not (found by tools/self_fuzz.py: `labels` + `classes`)
-  if (!(e[6] > a.conf_thres) || !class_allowed(a.cm, (int)e[7])) return;
-  const int slot = atomicAdd(&a.cnt[b * kCntPad], 1);
-  { const int fl = cand_flags(e[1], e[3], e[4], a.win_lo, a.win_hi); if (fl) atomicOr(&a.tiny[b], fl); }
-  if (slot >= a.cap_img) return;
-  const size_t g = (size_t)b * a.cap_img + slot;
-  a.cand[g * 2] = make_float4(e[1], e[2], e[3], e[4]);
-  a.cand[g * 2 + 1] = make_float4(e[5], e[6], e[7], 0.f);
-  a.keys[g] = ((unsigned long long)score_desc_key(e[6]) << 32) | (unsigned long long)(uint32_t)(A * nc + i);
-  a.vals[g] = (uint32_t)slot;
-}
 
 // Cross-class check of the images that hold short-sided boxes (kImgSmall, see the flag table above): every pair (short-sided
 // box T, box B of ANOTHER class) that rbox_pair_well_conditioned does not vouch for goes through the reference's own arithmetic
@@ -1404,7 +1027,7 @@ struct ObbCarve {
 
 static inline int64_t round_cap(int64_t cap_img) { return (cap_img + 63) / 64 * 64; }   // image regions start on alive-bitmap words
 
-static ObbCarve obb_carve(void* base, int64_t bs, int64_t cap_img, int64_t ncs) {
+static ObbCarve obb_carve(void* base, int64_t bs, int64_t cap_img, int64_t ncs, int cus) {
   cap_img = round_cap(cap_img);
   ObbCarve cv{};
   WsCursor w(base);
@@ -1419,201 +1042,293 @@ static ObbCarve obb_carve(void* base, int64_t bs, int64_t cap_img, int64_t ncs) 
   cv.srs_hist = w.take<uint32_t>((size_t)bs * ((size_t)(cap_img + kSrsTile - 1) / kSrsTile) * 256);
   cv.keep = w.take<int64_t>(n);
   // NMS state sized for bs * cap_img positions
-  w.nest([&](void* b) { return (cv.nms = carve(b, (int64_t)n, bs * ncs, RotGeom::RECQ, cap_max(bs * ncs))).total; });
+  w.nest([&](void* b) { return (cv.nms = carve(b, (int64_t)n, bs * ncs, RotGeom::RECQ, cap_max(bs * ncs), cus)).total; });
   cv.total = w.total();
   return cv;
 }
 
-// The front kernel that reads the Detect head's conv outputs instead of `pred` (nms_head.h, obb_non_max_suppression_obb_head)
-struct HeadFront;
-struct HeadFrontTta;
-static int launch_decode_head(const HeadFront& h, const DecodeArgs& d, int dtype, hipStream_t st);
-static int launch_decode_head_tta(const HeadFrontTta& h, const DecodeArgs& d, int dtype, hipStream_t st);
+// ---------------------------------------------------------------- the fused driver
+// One call, by name.  The front is ONE of: pred (+ objcol, the dense objectness column a coupled Detect decode left, or NULL);
+// head: the candidates come from the conv outputs it describes (k_decode_head) and pred / objcol are not read; tta: from the
+// (pass, level) entries of augmented inference (k_decode_head<T, true>), likewise.
+struct NmsObbCall {
+  const void* pred = nullptr; const void* objcol = nullptr;
+  const HeadFront* head = nullptr; const HeadFrontTta* tta = nullptr;
+  int dtype = 0;
+  int64_t bs = 0, A = 0, no = 0;
+  float conf_thres = 0.f, iou_thres = 0.f;
+  const int32_t* classes_host = nullptr; int n_classes = 0;
+  int agnostic = 0, multi_label = 0;
+  int64_t max_det = 0, max_nms = 0;
+  float max_wh = 0.f;
+  const float* extra8 = nullptr; int64_t n_extra = 0;      // the apriori label rows
+  int64_t cap_img = 0, expected_cand = 0;
+  float* out = nullptr; int out_packed = 0; int64_t* out_count = nullptr; int64_t* status = nullptr;
+  void* ws = nullptr; size_t ws_bytes = 0;
+  void* state = nullptr; size_t state_bytes = 0;            // caller-kept counters (obb_non_max_suppression_obb_st), or NULL
+  hipStream_t stream = nullptr;
+};
 
-// head != NULL: the candidates come from the conv outputs it describes (k_decode_head) and pred / objcol are not read;
-// tta != NULL: from the (pass, level) entries of augmented inference (k_decode_head<T, true>), likewise
-static int run_nms_obb(const void* pred, const void* objcol, int dtype, int64_t bs, int64_t A, int64_t no, float conf_thres, float iou_thres,
-                       const int32_t* classes_host, int n_classes, int agnostic, int multi_label, int64_t max_det, int64_t max_nms,
-                       float max_wh, const float* extra8, int64_t n_extra, int64_t cap_img, int64_t expected_cand, float* out,
-                       int out_packed, int64_t* out_count, int64_t* status, void* ws, size_t ws_bytes, hipStream_t st, void* state = nullptr,
-                       size_t state_bytes = 0, const HeadFront* head = nullptr, const HeadFrontTta* tta = nullptr) {
-  const int nc = (int)(no - 5 - 180);                              // :784
-  if (bs < 1 || A < 1 || nc < 1 || nc > 256 || max_det < 1 || cap_img < 1 || (!pred && !head && !tta) || !out || !out_count || !status)
-    return OBB_ERR_BAD_ARG;
-  if (A * nc + n_extra > 0xffffffffLL || bs * cap_img > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
-  if (!dtype_known(dtype)) return OBB_ERR_BAD_ARG;
-  cap_img = round_cap(cap_img);
-  ObbCarve cv = obb_carve(ws, bs, cap_img, agnostic ? 1 : nc);
-  if (!ws_ok(ws, ws_bytes, cv.total)) return OBB_ERR_WORKSPACE;
-  // the call's path (nms_plan.h): every choice below reads a field of the plan
-  ObbPlanIn pin{};
-  pin.bs = bs; pin.A = A; pin.nc = nc; pin.agnostic = agnostic; pin.multi_label = multi_label; pin.iou_thres = iou_thres; pin.max_wh = max_wh;
-  pin.n_extra = n_extra; pin.cap_img = cap_img; pin.max_nms = max_nms; pin.max_det = max_det; pin.expected_cand = expected_cand;
-  pin.out_packed = out_packed; pin.hw_cus = hw_cu_count(); pin.cus = cu_count(); pin.ecap = cv.nms.ecap;
-  pin.sort_tmp_bytes = cv.nms.sort_tmp_bytes; pin.ps_scratch_bytes = ps_scratch_bytes();
-  const ObbPlan plan = plan_nms_obb(pin, nms_env());
-  const int ncs = plan.ncs, class_ok = plan.class_ok, helpers = plan.helpers;
-  int rc = OBB_OK;
-  // caller-kept counters: zero when the call starts (the caller's memset, or the previous call's last kernel) -- no reset launch
-  const bool kept = state != nullptr;
-  if (kept) {
-    if (!ws_ok(state, state_bytes, obb_state_bytes(bs))) return OBB_ERR_WORKSPACE;
-    cv.cnt = (int*)state;
-    cv.tiny = cv.cnt + bs * kCntPad;
-  }
+// what the C entries of the fused driver have in common (nms.hip); each adds its front, and its state block if it takes one
+static NmsObbCall nms_obb_call(int dtype, int64_t bs, int64_t A, int64_t no, float conf_thres, float iou_thres, const int32_t* classes_host,
+                               int n_classes, int agnostic, int multi_label, int64_t max_det, int64_t max_nms, float max_wh,
+                               const float* extra8, int64_t n_extra, int64_t cap_img, int64_t expected_cand, float* out, int out_packed,
+                               int64_t* out_count, int64_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NmsObbCall c;
+  c.dtype = dtype; c.bs = bs; c.A = A; c.no = no; c.conf_thres = conf_thres; c.iou_thres = iou_thres;
+  c.classes_host = classes_host; c.n_classes = n_classes; c.agnostic = agnostic; c.multi_label = multi_label;
+  c.max_det = max_det; c.max_nms = max_nms; c.max_wh = max_wh; c.extra8 = extra8; c.n_extra = n_extra;
+  c.cap_img = cap_img; c.expected_cand = expected_cand; c.out = out; c.out_packed = out_packed ? 1 : 0; c.out_count = out_count;
+  c.status = status; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = (hipStream_t)stream;
+  return c;
+}
 
+// What the steps of a call hand to each other.  Nothing here is allocated: pointers into the caller's workspace, and the plan.
+struct NmsObbRun {
+  const NmsObbCall& c;
+  int nc;                    // :784
+  int64_t cap_img;           // rounded (round_cap)
+  DeviceCus dc;              // the current device, read once
+  ObbCarve cv;
+  ObbPlan plan;
+  bool kept;                 // caller-kept counters: cv.cnt / cv.tiny live in c.state
+  SmallHelpBlocks hb;        // k_nms_small's helper blocks (plan.helpers > 0)
+  long long bar16, alive16;  // 16-byte pieces of the barrier block / the alive bitmap that the call's first kernel zeroes
   DecodeArgs d;
-  d.pred = pred; d.objcol = objcol; d.A = A; d.no = (int)no; d.nc = nc; d.bs = (int)bs; d.conf_thres = conf_thres;
-  d.multi_label = plan.multi_label;
-  d.cm.all = (classes_host == nullptr || n_classes <= 0) ? 1 : 0;
-  for (int i = 0; i < 4; i++) d.cm.w[i] = 0ull;
-  for (int i = 0; i < n_classes && classes_host; i++) {
-    int c = classes_host[i];
-    if (c >= 0 && c < 256) d.cm.w[c >> 6] |= 1ull << (c & 63);
-  }
-  d.cap_img = cap_img; d.cand = cv.cand; d.keys = cv.keys_a; d.vals = cv.vals_a; d.cnt = cv.cnt; d.tiny = cv.tiny;
-  d.win_lo = -0.35f * max_wh; d.win_hi = 0.6f * max_wh;            // 0.95 max_wh wide: circles of different classes cannot touch
+};
 
-  d.z_ticket = nullptr; d.n_ticket = 0; d.z_bar16 = nullptr; d.n_bar16 = 0; d.z_alive16 = nullptr; d.n_alive16 = 0;
-  {
-    Carve& nv0 = cv.nms;
-    // (cap_img is a multiple of 64 -> bs * cap_img / 64 words; + the guard words, rounded up to 16 bytes)
-    // only what the planned path reads (plan.zero_bar / zero_alive): the headline's self-sorting segments need neither block
-    const long long alive16 = plan.zero_alive ? (long long)((((size_t)bs * cap_img) >> 6) + 8 + 1) / 2 : 0ll;
-    const long long bar16 = plan.zero_bar ? (long long)(nv0.bar_bytes / 16) : 0ll;
-    if (kept) {                                                    // the filter kernel zeroes what the later launches need
-      d.z_ticket = cv.ticket; d.n_ticket = (int)(16 + bs + 1);
-      d.z_bar16 = bar16 ? reinterpret_cast<uint4*>(nv0.bar) : nullptr; d.n_bar16 = bar16;
-      d.z_alive16 = alive16 ? reinterpret_cast<uint4*>(nv0.alive) : nullptr; d.n_alive16 = alive16;
-    } else {
-      k_reset_state<<<256, 256, 0, st>>>(cv.cnt, (int)(bs * kCntPad), cv.tiny, (int)bs, status, cv.ticket, (int)(16 + bs + 1),
-                                         reinterpret_cast<uint4*>(nv0.bar), bar16, reinterpret_cast<uint4*>(nv0.alive), alive16);
-    }
+// ---- 1. argument checks: OBB_ERR_BAD_ARG before the workspace is looked at
+static int obb_check_args(const NmsObbCall& c) {
+  const int nc = (int)(c.no - 5 - 180);                            // :784
+  if (c.bs < 1 || c.A < 1 || nc < 1 || nc > 256 || c.max_det < 1 || c.cap_img < 1 || (!c.pred && !c.head && !c.tta) || !c.out ||
+      !c.out_count || !c.status)
+    return OBB_ERR_BAD_ARG;
+  if (c.A * nc + c.n_extra > 0xffffffffLL || c.bs * c.cap_img > 0x7fffffffLL) return OBB_ERR_BAD_ARG;
+  if (!dtype_known(c.dtype)) return OBB_ERR_BAD_ARG;
+  return OBB_OK;
+}
+
+// ---- 2. the workspace layout and its size check
+static int obb_carve_call(NmsObbRun& r) {
+  const NmsObbCall& c = r.c;
+  r.nc = (int)(c.no - 5 - 180);
+  r.cap_img = round_cap(c.cap_img);
+  r.dc = device_cus();
+  r.cv = obb_carve(c.ws, c.bs, r.cap_img, c.agnostic ? 1 : r.nc, r.dc.cus);
+  return ws_ok(c.ws, c.ws_bytes, r.cv.total) ? OBB_OK : OBB_ERR_WORKSPACE;
+}
+
+// ---- 3. the call's path (nms_plan.h): every choice of the later steps reads a field of the plan.  The caller-kept counters are
+// bound here, behind the plan, where their size has always been checked.
+static int obb_plan_call(NmsObbRun& r) {
+  const NmsObbCall& c = r.c;
+  ObbCarve& cv = r.cv;
+  ObbPlanIn pin{};
+  pin.bs = c.bs; pin.A = c.A; pin.nc = r.nc; pin.agnostic = c.agnostic; pin.multi_label = c.multi_label; pin.iou_thres = c.iou_thres; pin.max_wh = c.max_wh;
+  pin.n_extra = c.n_extra; pin.cap_img = r.cap_img; pin.max_nms = c.max_nms; pin.max_det = c.max_det; pin.expected_cand = c.expected_cand;
+  pin.out_packed = c.out_packed; pin.hw_cus = r.dc.hw_cus; pin.cus = r.dc.cus; pin.ecap = cv.nms.ecap;
+  pin.sort_tmp_bytes = cv.nms.sort_tmp_bytes; pin.ps_scratch_bytes = ps_scratch_bytes();
+  r.plan = plan_nms_obb(pin, nms_env());
+  // caller-kept counters: zero when the call starts (the caller's memset, or the previous call's last kernel) -- no reset launch
+  r.kept = c.state != nullptr;
+  if (r.kept) {
+    if (!ws_ok(c.state, c.state_bytes, obb_state_bytes(c.bs))) return OBB_ERR_WORKSPACE;
+    cv.cnt = (int*)c.state;
+    cv.tiny = cv.cnt + c.bs * kCntPad;
   }
-  d.rows_per_thread = plan.rows_per_thread;
-  dim3 gd((unsigned)((A + kDecThreads * d.rows_per_thread - 1) / (kDecThreads * d.rows_per_thread)), (unsigned)bs);
+  // k_nms_small's helper blocks live in the persistent kernel's edge lists, which that path does not use (the plan has checked the fit)
+  r.hb = SmallHelpBlocks{};
+  if (r.plan.helpers > 0) { WsCursor w(cv.nms.edges); r.hb = small_help_layout(w, r.plan.helpers, c.bs * r.plan.ncs, c.bs * r.cap_img); }
+  return OBB_OK;
+}
+
+// ---- 4. the front kernel's arguments: class filter, candidate blocks, and the state of the later launches it zeroes on its way
+static void obb_fill_decode(NmsObbRun& r) {
+  const NmsObbCall& c = r.c;
+  const ObbCarve& cv = r.cv;
+  DecodeArgs& d = r.d;
+  d.pred = c.pred; d.objcol = c.objcol; d.A = c.A; d.no = (int)c.no; d.nc = r.nc; d.bs = (int)c.bs; d.conf_thres = c.conf_thres;
+  d.multi_label = r.plan.multi_label;
+  d.rows_per_thread = r.plan.rows_per_thread;
+  class_mask_fill(c.classes_host, c.n_classes, d.cm.w, &d.cm.all);
+  d.cap_img = r.cap_img; d.cand = cv.cand; d.keys = cv.keys_a; d.vals = cv.vals_a; d.cnt = cv.cnt; d.tiny = cv.tiny;
+  d.win_lo = -0.35f * c.max_wh; d.win_hi = 0.6f * c.max_wh;        // 0.95 max_wh wide: circles of different classes cannot touch
+  // (cap_img is a multiple of 64 -> bs * cap_img / 64 words; + the guard words, rounded up to 16 bytes)
+  // only what the planned path reads (plan.zero_bar / zero_alive): the headline's self-sorting segments need neither block
+  r.alive16 = r.plan.zero_alive ? (long long)((((size_t)c.bs * r.cap_img) >> 6) + 8 + 1) / 2 : 0ll;
+  r.bar16 = r.plan.zero_bar ? (long long)(cv.nms.bar_bytes / 16) : 0ll;
+  d.z_ticket = nullptr; d.n_ticket = 0; d.z_bar16 = nullptr; d.n_bar16 = 0; d.z_alive16 = nullptr; d.n_alive16 = 0;
+  if (r.kept) {                                                    // the filter kernel zeroes what the later launches need
+    d.z_ticket = cv.ticket; d.n_ticket = (int)(16 + c.bs + 1);
+    d.z_bar16 = r.bar16 ? reinterpret_cast<uint4*>(cv.nms.bar) : nullptr; d.n_bar16 = r.bar16;
+    d.z_alive16 = r.alive16 ? reinterpret_cast<uint4*>(cv.nms.alive) : nullptr; d.n_alive16 = r.alive16;
+  }
+}
+
+// ---- 5. the front: the reset launch of a call without caller-kept counters, the filter kernel of the call's front, the label
+// rows, and the cross-class check of short-sided boxes when the previous call met some
+static int obb_front_stage(NmsObbRun& r) {
+  const NmsObbCall& c = r.c;
+  const ObbCarve& cv = r.cv;
+  const DecodeArgs& d = r.d;
+  hipStream_t st = c.stream;
+  if (!r.kept)
+    k_reset_state<<<256, 256, 0, st>>>(cv.cnt, (int)(c.bs * kCntPad), cv.tiny, (int)c.bs, c.status, cv.ticket, (int)(16 + c.bs + 1),
+                                       reinterpret_cast<uint4*>(cv.nms.bar), r.bar16, reinterpret_cast<uint4*>(cv.nms.alive), r.alive16);
+  dim3 gd((unsigned)((c.A + kDecThreads * d.rows_per_thread - 1) / (kDecThreads * d.rows_per_thread)), (unsigned)c.bs);
   {
     ProfScope ps(PROF_DECODE, st);
-    if (head || tta) {
-      rc = head ? launch_decode_head(*head, d, dtype, st) : launch_decode_head_tta(*tta, d, dtype, st);
+    if (c.head || c.tta) {
+      const int rc = c.head ? launch_decode_head(*c.head, d, c.dtype, r.dc.dev, st) : launch_decode_head_tta(*c.tta, d, c.dtype, r.dc.dev, st);
       if (rc) return rc;
-    } else OBB_DISPATCH_DTYPE(dtype, T, k_decode<T><<<gd, kDecThreads, 0, st>>>(d));
+    } else OBB_DISPATCH_DTYPE(c.dtype, T, k_decode<T><<<gd, kDecThreads, 0, st>>>(d));
   }
-  if (n_extra > 0 && extra8) k_append_extra<<<(unsigned)((n_extra + 255) / 256), 256, 0, st>>>(extra8, (int)n_extra, A, nc, d);
-  if (plan.small_hint && class_ok)
-    k_tiny_cross<<<dim3(kTinyParts, (unsigned)bs), 256, 0, st>>>(cv.cand, cv.keys_a, cv.cnt, cap_img, max_wh, iou_thres, cv.tiny);
-  const unsigned gs = (unsigned)((bs + 255) / 256);
-  Carve& nv = cv.nms;
-  const int64_t max_seg = plan.max_seg;
-  // k_nms_small's helper blocks live in the persistent kernel's edge lists, which that path does not use (the plan has checked the fit)
-  SmallHelpBlocks hb{};
-  if (helpers > 0) { WsCursor w(nv.edges); hb = small_help_layout(w, helpers, bs * ncs, bs * cap_img); }
-  if (plan.self_sort) {                                           // no sort launch: k_nms_small orders its segments itself
-  } else if (plan.lds_sort) {
+  if (c.n_extra > 0 && c.extra8) k_append_extra<<<(unsigned)((c.n_extra + 255) / 256), 256, 0, st>>>(c.extra8, (int)c.n_extra, c.A, r.nc, d);
+  if (r.plan.small_hint && r.plan.class_ok)
+    k_tiny_cross<<<dim3(kTinyParts, (unsigned)c.bs), 256, 0, st>>>(cv.cand, cv.keys_a, cv.cnt, r.cap_img, c.max_wh, c.iou_thres, cv.tiny);
+  return OBB_OK;
+}
+
+// ---- 6. the sort stage: nothing (k_nms_small orders its segments itself), the in-LDS sort with segment table and records in one
+// launch, or segment bookkeeping + radix / three-launch sort + class bounds + records
+static int obb_sort_stage(NmsObbRun& r) {
+  const NmsObbCall& c = r.c;
+  const ObbCarve& cv = r.cv;
+  const Carve& nv = cv.nms;
+  const ObbPlan& plan = r.plan;
+  const SmallHelpBlocks& hb = r.hb;
+  hipStream_t st = c.stream;
+  const int64_t bs = c.bs, A = c.A, cap_img = r.cap_img, max_nms = c.max_nms;
+  const int nc = r.nc, ncs = plan.ncs, class_ok = plan.class_ok, helpers = plan.helpers, agnostic = c.agnostic;
+  const float max_wh = c.max_wh;
+  if (plan.self_sort) return OBB_OK;                              // no sort launch: k_nms_small orders its segments itself
+  if (plan.lds_sort) {
     ProfScope ps(PROF_SEGSORT, st);
     static OncePerDevice attr;
     const size_t lds = (size_t)kSortLdsMax * 12;
-    if (const int attr_dev = attr.need(); attr_dev != OncePerDevice::kDone) {
-      if (hipFuncSetAttribute((const void*)k_sort_prep_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return OBB_ERR_LAUNCH;
-      attr.mark(attr_dev);
-    }
+    if (!raise_lds_once_on(r.dc.dev, attr, lds, k_sort_prep_lds)) return OBB_ERR_LAUNCH;
     k_sort_prep_lds<<<(unsigned)(bs * plan.parts) + (plan.plan_nb > 0 ? 1u : 0u), 1024, lds, st>>>(cv.cand, cv.keys_a, cv.vals_a, cv.keys_b, cv.vals_b, cv.cnt, cv.tiny, (int)bs, cap_img,
                                                    max_nms, class_ok, A, nc, ncs, agnostic ? 0.f : max_wh, cv.sort_begin, cv.sort_end,
                                                    cv.img_end, cv.mode, nv.seg_begin, nv.seg_end, nv.keep_cnt,
                                                    nv.rec, nv.alive, cv.ticket, plan.plan_nb, plan.plan_chunk, plan.plan_nb > 0 ? nv.plan : nullptr,
                                                    cv.seg_size, plan.parts,
                                                    helpers, hb.work, hb.seg_np, hb.seg_ticket);
-  } else {
-   {
+    return OBB_OK;
+  }
+  {
     ProfScope ps(PROF_SEGSORT, st);
+    const unsigned gs = (unsigned)((bs + 255) / 256);
     k_cand_segments<<<gs, 256, 0, st>>>(cv.cnt, cv.tiny, (int)bs, cap_img, max_nms, class_ok, cv.sort_begin, cv.sort_end, cv.img_end,
                                         cv.mode);
     if (class_ok) {
       dim3 gr((unsigned)((cap_img + 255) / 256), (unsigned)bs);
       k_rekey<<<gr, 256, 0, st>>>(cv.cand, cv.keys_a, cv.sort_begin, cv.sort_end, cv.mode, A, nc);
     }
-    {
-      // the radix sort of segsort.h, or the three-launch sort of psrs_sort.h over ONE large image's candidates (nms_plan.h)
-      if (plan.psrs) {
-        PsBuf b{};
-        b.run_k = cv.keys_a; b.run_v = cv.vals_a; b.out_k = cv.keys_b; b.out_v = cv.vals_b;      // (the runs are sorted in place)
-        b.n = (int)cap_img; b.n_dev = cv.sort_end; b.err = nullptr;
-        ps_carve_scratch(nv.sort_tmp, &b);
-        const int runs = (int)((cap_img + kPsRun - 1) / kPsRun);
-        k_ps_local_pairs<<<(unsigned)runs, kPsRun, 0, st>>>(b, cv.keys_a, cv.vals_a);
-        rc = ps_finish(b, runs, st);
-        if (rc) return rc;
-      } else {
-        rc = seg_radix_sort_large(cv.keys_a, cv.keys_b, cv.vals_a, cv.vals_b, cv.sort_begin, cv.sort_end, (int)bs, cap_img, bs * cap_img,
-                                  plan.radix_mask, cv.srs_hist, st);
-        if (rc) return rc;
-      }
+    // the radix sort of segsort.h, or the three-launch sort of psrs_sort.h over ONE large image's candidates (nms_plan.h)
+    if (plan.psrs) {
+      PsBuf b{};
+      b.run_k = cv.keys_a; b.run_v = cv.vals_a; b.out_k = cv.keys_b; b.out_v = cv.vals_b;      // (the runs are sorted in place)
+      b.n = (int)cap_img; b.n_dev = cv.sort_end; b.err = nullptr;
+      ps_carve_scratch(nv.sort_tmp, &b);
+      const int runs = (int)((cap_img + kPsRun - 1) / kPsRun);
+      k_ps_local_pairs<<<(unsigned)runs, kPsRun, 0, st>>>(b, cv.keys_a, cv.vals_a);
+      if (const int rc = ps_finish(b, runs, st)) return rc;
+    } else {
+      if (const int rc = seg_radix_sort_large(cv.keys_a, cv.keys_b, cv.vals_a, cv.vals_b, cv.sort_begin, cv.sort_end, (int)bs, cap_img, bs * cap_img,
+                                              plan.radix_mask, cv.srs_hist, st))
+        return rc;
     }
     const int64_t nseg = bs * ncs;
     k_class_bounds<<<(unsigned)((nseg + 255) / 256), 256, 0, st>>>(cv.keys_b, cv.sort_begin, cv.img_end, cv.mode, (int)bs, ncs,
                                                                    nv.seg_begin, nv.seg_end, nv.keep_cnt);
-   }
-   dim3 gp((unsigned)((max_seg + 255) / 256), (unsigned)bs);
-   {
+  }
+  dim3 gp((unsigned)((plan.max_seg + 255) / 256), (unsigned)bs);
+  {
     ProfScope ps(PROF_PREP, st);
     if (hipMemsetAsync(nv.alive, 0, nv.alive_bytes, st) != hipSuccess) return OBB_ERR_LAUNCH;
     k_prep_cand<<<gp, 256, 0, st>>>(cv.cand, cv.vals_b, cv.sort_begin, cv.img_end, cap_img, agnostic ? 0.f : max_wh, nv.rec, nv.alive);
-   }
   }
+  return OBB_OK;
+}
 
-  NmsArgs a{};
-  nms_args_from(nv, cap_max(bs * ncs), &a);
-  a.order = nullptr; a.keep_out = cv.keep; a.n = (int)(bs * cap_img);                  // keep_out: sorted positions
-  a.max_keep = (int)max_det; a.window = plan.window; a.thr = iou_thres; a.cull = (iou_thres >= 0.f) ? 1 : 0;
-  if (plan.small_nms) {
-    ProfScope ps(PROF_STEPS, st);
-    static OncePerDevice attr;
-    const size_t lds = small_lds_bytes<RotGeom>();
-    if (const int attr_dev = attr.need(); attr_dev != OncePerDevice::kDone) {
-      if (hipFuncSetAttribute((const void*)k_nms_small<RotGeom, SmallNoTail>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_nms_small<RotGeom, SmallGather>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_nms_small<RotGeom, SmallGather, SmallSelfSort>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return OBB_ERR_LAUNCH;
-      attr.mark(attr_dev);
-    }
-    SmallArgs sa{};
-    sa.rec = nv.rec; sa.alive = nv.alive; sa.seg_begin = nv.seg_begin; sa.seg_end = nv.seg_end; sa.keep_cnt = nv.keep_cnt;
-    sa.keep_out = cv.keep; sa.too_big = cv.ticket + 8; sa.thr = iou_thres; sa.max_keep = (int)max_det;
-    sa.ncs = ncs; sa.mode = cv.mode;
-    sa.helpers = helpers; sa.help_cnt = cv.ticket + 12; sa.work = hb.work; sa.seg_np = hb.seg_np; sa.seg_ticket = hb.seg_ticket;
-    sa.part_main = hb.part_main; sa.part_help = hb.part_help;
-    const unsigned gsmall = (unsigned)(bs * ncs + helpers);      // (the helpers are the FIRST blocks: dispatched before the segments' own workgroups)
-    if (plan.fused_out) {                                        // the output stage runs inside k_nms_small (SmallGather)
-      // (keys_a / vals_a, the sort's input, are free: they take what the segments publish)
-      sa.keys_sorted = cv.keys_b; sa.vals_sorted = cv.vals_b; sa.pub_key = cv.keys_a; sa.pub_val = cv.vals_a; sa.n_pos = bs * cap_img;
-      SmallGather::Args ga{};
-      ga.cand = cv.cand; ga.cnt = cv.cnt; ga.tiny = cv.tiny; ga.info = cv.ticket; ga.ticket = cv.ticket + 16;
-      ga.out = out; ga.out_count = out_count; ga.status = status; ga.cap_img = cap_img; ga.max_det = max_det; ga.bs = (int)bs;
-      ga.clean_cnt = kept ? cv.cnt : nullptr; ga.clean_tiny = kept ? cv.tiny : nullptr;
-      if (plan.self_sort) {
-        // (the segments read keys_a, the filter kernel's output, while others publish: keys_b / vals_b, the sort's output places, are free)
-        sa.pub_key = cv.keys_b; sa.pub_val = cv.vals_b; sa.keys_sorted = nullptr; sa.vals_sorted = nullptr;
-        sa.keys_in = cv.keys_a; sa.cand = cv.cand; sa.cnt = cv.cnt; sa.tiny = cv.tiny; sa.cap_img = cap_img; sa.max_nms = max_nms; sa.A = A; sa.nc = nc;
-        sa.class_offset = max_wh; sa.seg_max = cv.ticket + 4;
-        k_nms_small<RotGeom, SmallGather, SmallSelfSort><<<gsmall, kSmallThreads, lds, st>>>(sa, ga);
-      } else
-      k_nms_small<RotGeom, SmallGather><<<gsmall, kSmallThreads, lds, st>>>(sa, ga);
-    } else {
-      k_nms_small<RotGeom, SmallNoTail><<<gsmall, kSmallThreads, lds, st>>>(sa, SmallNoTail::Args{});
-    }
-  } else {
-    ProfScope ps(PROF_STEPS, st);
-    rc = nms_steps(0, a, nv, bs * ncs, bs * max_seg, st, kNmsBarZeroed | ((plan.lds_sort && plan.plan_nb > 0) ? kNmsPlanned : 0));
-    if (rc) return rc;
+// ---- 7. the NMS stage: k_nms_small (one workgroup per segment; with its output stage inside unless the rows are packed), or
+// the persistent kernel
+static int obb_nms_stage(NmsObbRun& r) {
+  const NmsObbCall& c = r.c;
+  const ObbCarve& cv = r.cv;
+  const Carve& nv = cv.nms;
+  const ObbPlan& plan = r.plan;
+  const SmallHelpBlocks& hb = r.hb;
+  hipStream_t st = c.stream;
+  const int64_t bs = c.bs, cap_img = r.cap_img, max_det = c.max_det;
+  const int ncs = plan.ncs, helpers = plan.helpers;
+  ProfScope ps(PROF_STEPS, st);
+  if (!plan.small_nms) {
+    NmsArgs a{};
+    nms_args_from(nv, cap_max(bs * ncs), &a);
+    a.order = nullptr; a.keep_out = cv.keep; a.n = (int)(bs * cap_img);                  // keep_out: sorted positions
+    a.max_keep = (int)max_det; a.window = plan.window; a.thr = c.iou_thres; a.cull = (c.iou_thres >= 0.f) ? 1 : 0;
+    return nms_steps(0, a, nv, bs * ncs, bs * plan.max_seg, r.dc, st, kNmsBarZeroed | ((plan.lds_sort && plan.plan_nb > 0) ? kNmsPlanned : 0));
   }
+  static OncePerDevice attr;
+  const size_t lds = small_lds_bytes<RotGeom>();
+  if (!raise_lds_once_on(r.dc.dev, attr, lds, k_nms_small<RotGeom, SmallNoTail>, k_nms_small<RotGeom, SmallGather>, k_nms_small<RotGeom, SmallGather, SmallSelfSort>))
+    return OBB_ERR_LAUNCH;
+  SmallArgs sa{};
+  sa.rec = nv.rec; sa.alive = nv.alive; sa.seg_begin = nv.seg_begin; sa.seg_end = nv.seg_end; sa.keep_cnt = nv.keep_cnt;
+  sa.keep_out = cv.keep; sa.too_big = cv.ticket + 8; sa.thr = c.iou_thres; sa.max_keep = (int)max_det;
+  sa.ncs = ncs; sa.mode = cv.mode;
+  sa.helpers = helpers; sa.help_cnt = cv.ticket + 12; sa.work = hb.work; sa.seg_np = hb.seg_np; sa.seg_ticket = hb.seg_ticket;
+  sa.part_main = hb.part_main; sa.part_help = hb.part_help;
+  const unsigned gsmall = (unsigned)(bs * ncs + helpers);      // (the helpers are the FIRST blocks: dispatched before the segments' own workgroups)
   if (!plan.fused_out) {
+    k_nms_small<RotGeom, SmallNoTail><<<gsmall, kSmallThreads, lds, st>>>(sa, SmallNoTail::Args{});
+    return OBB_OK;
+  }
+  // the output stage runs inside k_nms_small (SmallGather)
+  // (keys_a / vals_a, the sort's input, are free: they take what the segments publish)
+  sa.keys_sorted = cv.keys_b; sa.vals_sorted = cv.vals_b; sa.pub_key = cv.keys_a; sa.pub_val = cv.vals_a; sa.n_pos = bs * cap_img;
+  SmallGather::Args ga{};
+  ga.cand = cv.cand; ga.cnt = cv.cnt; ga.tiny = cv.tiny; ga.info = cv.ticket; ga.ticket = cv.ticket + 16;
+  ga.out = c.out; ga.out_count = c.out_count; ga.status = c.status; ga.cap_img = cap_img; ga.max_det = max_det; ga.bs = (int)bs;
+  ga.clean_cnt = r.kept ? cv.cnt : nullptr; ga.clean_tiny = r.kept ? cv.tiny : nullptr;
+  if (plan.self_sort) {
+    // (the segments read keys_a, the filter kernel's output, while others publish: keys_b / vals_b, the sort's output places, are free)
+    sa.pub_key = cv.keys_b; sa.pub_val = cv.vals_b; sa.keys_sorted = nullptr; sa.vals_sorted = nullptr;
+    sa.keys_in = cv.keys_a; sa.cand = cv.cand; sa.cnt = cv.cnt; sa.tiny = cv.tiny; sa.cap_img = cap_img; sa.max_nms = c.max_nms; sa.A = c.A; sa.nc = r.nc;
+    sa.class_offset = c.max_wh; sa.seg_max = cv.ticket + 4;
+    k_nms_small<RotGeom, SmallGather, SmallSelfSort><<<gsmall, kSmallThreads, lds, st>>>(sa, ga);
+  } else {
+    k_nms_small<RotGeom, SmallGather><<<gsmall, kSmallThreads, lds, st>>>(sa, ga);
+  }
+  return OBB_OK;
+}
+
+// ---- 8. the output stage, unless k_nms_small had it inside; the call's launch errors are collected here
+static int obb_output_stage(NmsObbRun& r) {
+  const NmsObbCall& c = r.c;
+  const ObbCarve& cv = r.cv;
+  hipStream_t st = c.stream;
+  if (!r.plan.fused_out) {
     ProfScope ps(PROF_GATHER, st);
-    k_gather_out<<<dim3((unsigned)bs, plan.gparts), 256, 0, st>>>(cv.cand, cv.vals_b, cv.keys_b, cv.keep, nv.seg_begin, nv.keep_cnt, cv.mode, ncs, max_det,
-                                              out, out_count, cv.cnt, cap_img, status, nv.abort_flag, out_packed, cv.ticket, cv.tiny,
-                                              kept ? cv.cnt : nullptr, kept ? cv.tiny : nullptr);
+    k_gather_out<<<dim3((unsigned)c.bs, r.plan.gparts), 256, 0, st>>>(cv.cand, cv.vals_b, cv.keys_b, cv.keep, cv.nms.seg_begin, cv.nms.keep_cnt, cv.mode, r.plan.ncs, c.max_det,
+                                              c.out, c.out_count, cv.cnt, r.cap_img, c.status, cv.nms.abort_flag, c.out_packed, cv.ticket, cv.tiny,
+                                              r.kept ? cv.cnt : nullptr, r.kept ? cv.tiny : nullptr);
   }
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
 }
 
+static int run_nms_obb(const NmsObbCall& c) {
+  if (const int rc = obb_check_args(c)) return rc;
+  NmsObbRun r{c};
+  if (const int rc = obb_carve_call(r)) return rc;
+  if (const int rc = obb_plan_call(r)) return rc;
+  obb_fill_decode(r);
+  if (const int rc = obb_front_stage(r)) return rc;
+  if (const int rc = obb_sort_stage(r)) return rc;
+  if (const int rc = obb_nms_stage(r)) return rc;
+  return obb_output_stage(r);
+}
+
 }  // namespace obb
+

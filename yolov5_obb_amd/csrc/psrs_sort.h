@@ -1,4 +1,4 @@
-// Device-wide sort of (u64 key, u32 value) pairs with UNIQUE keys -- gfx950 (included by nms.hip, namespace obb).
+// Device-wide sort of (u64 key, u32 value) pairs with UNIQUE keys -- gfx950 (namespace obb).
 //
 // Replaces the library sort in front of the NMS (nms_rotated_cuda.cu:81-82: scores.sort(0, descending) + index_select) for
 // lists of up to kPsMaxN elements.  Parallel sorting by regular sampling in three launches, no workgroup ever waits for
@@ -19,7 +19,13 @@
 // unique (score bits in the high word, original index / tie word in the low one), which IS the reference's documented
 // order here -- descending score, ties by ascending index.  Lists longer than kPsMaxN take segsort.h's LSD radix sort.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "launch_once.h"
 #include "nms_limits.h"
+#include "obb_device.h"
+#include "obb_hip.h"
 
 namespace obb {
 
@@ -339,10 +345,7 @@ static inline void ps_carve_scratch(void* scratch, PsBuf* b) {
 // launches 2 and 3 (the caller has launched its k_ps_local_* flavour over `runs` workgroups)
 static int ps_finish(const PsBuf& b, int runs, hipStream_t st) {
   static OncePerDevice attr;
-  if (const int attr_dev = attr.need(); attr_dev != OncePerDevice::kDone) {
-    if (hipFuncSetAttribute((const void*)k_ps_bucket, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPsBucketLds) != hipSuccess) return OBB_ERR_LAUNCH;
-    attr.mark(attr_dev);
-  }
+  if (!raise_lds_once(attr, kPsBucketLds, k_ps_bucket)) return OBB_ERR_LAUNCH;
   if (runs > 1) k_ps_split<<<(unsigned)runs, kPsRun, 0, st>>>(b);
   k_ps_bucket<<<(unsigned)runs, kPsRun, kPsBucketLds, st>>>(b);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;

@@ -1,4 +1,4 @@
-// Segmented LSD radix sort of (u64 key, u32 value) pairs for LARGE segments -- gfx950 (included by nms.hip, namespace obb).
+// Segmented LSD radix sort of (u64 key, u32 value) pairs for LARGE segments -- gfx950 (namespace obb).
 //
 // Why: a sort that gives every segment to ONE workgroup (the library's segmented sort, used in round 1; the in-LDS path of
 // the fused driver) is the right shape for the speed-test regime (16 images x ~2k candidates: 0.04 ms) and the wrong one for
@@ -9,6 +9,11 @@
 // same digit find each other with 8 ballots, so the order inside a digit is the input order).  Passes over digits that
 // are constant for the whole call (unused tie / class bits) are skipped by the host.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "obb_device.h"
+#include "obb_hip.h"
 
 namespace obb {
 

@@ -293,7 +293,7 @@ template <class Launch>
 std::vector<at::Tensor> run_fused(const at::Device dev, int64_t bs, int64_t A, int64_t nc, bool multi, double conf_thres, bool agnostic,
                                   int64_t max_det, int64_t n_extra, Launch&& launch) {
   std::vector<at::Tensor> result;
-  static thread_local std::map<std::tuple<int64_t, int64_t, int64_t, int, bool>, size_t> ws_memo;
+  static thread_local std::map<std::tuple<int, int64_t, int64_t, int64_t, int, bool>, size_t> ws_memo;   // (the size depends on the device's CUs)
   obb_nms_obb_hints& hints = hints_of(shape_key((int)dev.index(), A, nc, multi, conf_thres));
   const int64_t worst = A * (multi ? nc : 1) + n_extra;
   int64_t cap = api.obb_nms_obb_hints_cap(&hints, worst);
@@ -305,7 +305,7 @@ std::vector<at::Tensor> run_fused(const at::Device dev, int64_t bs, int64_t A, i
   Pinned& meta = pinned_words(dev.index(), 1, bs + 2);                                                 // counts[bs] + status[2]
   AbortRetry retry;
   for (bool done = false; !done;) {
-    const auto wkey = std::make_tuple(bs, cap, nc, (int)agnostic, retry.capped);
+    const auto wkey = std::make_tuple((int)dev.index(), bs, cap, nc, (int)agnostic, retry.capped);
     auto it = ws_memo.find(wkey);
     if (it == ws_memo.end()) it = ws_memo.emplace(wkey, api.obb_nms_obb_workspace_bytes(bs, cap, nc, agnostic ? 1 : 0)).first;
     at::Tensor ws = workspace(it->second, dev);

@@ -20,7 +20,7 @@ _POLL_SECONDS = 2e-3  # busy-poll this long (a bs16 step is ~0.2 ms), then yield
 _POLL_GIVE_UP = 1.0   # ... after this many seconds: fall back to a stream synchronise
 _MAX_NMS = 30000    # utils/general.py:794
 _CSL = 180          # utils/general.py:784
-_ws_memo = {}       # (bs, cap, nc, agnostic, grid capped) -> workspace bytes (a ctypes call saved per batch)
+_ws_memo = {}       # (device index, bs, cap, nc, agnostic, grid capped) -> workspace bytes (a ctypes call saved per batch)
 _meta_memo = {}     # (device index, bs, thread) -> the int64 buffer the counters are read back from
 _SEG_SMALL = 384    # include/obb_hip.h OBB_NMS_SMALL_SEG: the one-workgroup-per-segment kernel of csrc/nms_small.h takes segments up to this size
 _HINTS_DONE, _HINTS_RETRY, _HINTS_RETRY_SMALL_GRID = 0, 1, 2   # include/obb_hip.h OBB_HINTS_*: what obb_nms_obb_hints_update answers
@@ -245,7 +245,7 @@ def _run_fused(launch, dev, bs, A, nc, multi, conf_thres, n_extra, agn, max_det)
             meta_np.fill(_PENDING)
             with _lib.guard(dev):
                 st = _lib.stream_handle(dev)
-                wkey = (bs, cap.value, nc, agn, capped)    # (the library sizes the workspace from the calling thread's grid cap)
+                wkey = (dev.index, bs, cap.value, nc, agn, capped)    # (the library sizes the workspace from the current device's CUs and the calling thread's grid cap)
                 nbytes = _ws_memo.get(wkey)
                 if nbytes is None:
                     nbytes = _ws_memo[wkey] = L.obb_nms_obb_workspace_bytes(bs, cap.value, nc, agn)
