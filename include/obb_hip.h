@@ -177,6 +177,43 @@ int obb_merge_nms_hbb_f64(const double* dets, int64_t row_stride, int64_t n, con
                           int64_t nseg, double thresh, int64_t* keep_out, int64_t* num_keep, void* ws, size_t ws_bytes, void* stream);
 
 /*
+ * In-memory tile -> full-image merge: from the per-tile outputs of non_max_suppression_obb straight to the merged detections of
+ * the source images, without the text hand-off of the reference's workflow (val.py:50-66 save_one_json ->
+ * tools/TestJson2VocClassTxt.py -> DOTA_devkit/ResultMerge_multi_process.py:183-234).  Per row, in the reference's order:
+ * rbox2poly and scale_polys in float32 (the bits of obb_val_postprocess_f32's pred_polyn), with OBB_TILE_MERGE_TEXT_ROUNDING
+ * Python's round(x, 1) of the coordinates and round(conf, 5) of the score as the text carries them (csrc/tile_merge_math.h),
+ * poly2origpoly (v + left | up) / rate in double; then the merge NMS of obb_merge_nms_poly_f64 (OBB_TILE_MERGE_POLY_ALL:
+ * obb_merge_nms_poly_all_f64) per (source image, class).
+ *   det7          (n, 7) fp32 device rows [cx cy l s theta conf cls], the tiles back to back, n = det_off_host[ntile]
+ *   det_off_host  (ntile + 1) int64 host: tile t owns rows det_off_host[t] .. det_off_host[t + 1]; [0] = 0, ascending
+ *   tiles_host    (ntile) obb_tile_rec host: source image in [0, n_src), the tile's origin in the (resized) image, the resize rate
+ *                 of its name (> 0), and scale_polys' pad and gain (gain > 0; 0, 0, 1 for a tile fed at the model's size)
+ *   thresh        the merge threshold, a Python float (nms_thresh = 0.2 in the reference)
+ *   out           (n, 11) doubles, the first sum(out_count) rows written: [8 source-image coordinates, score, cls, src_image],
+ *                 source image ascending, class ascending, processing order inside
+ *   out_count     (n_src * nc) int64: kept rows of segment src_image * nc + cls
+ *   info          (2) int32: [0] != 0: some row's class is not an integer in [0, nc) (it was counted as class 0; the result is
+ *                 invalid); [1] != 0: the NMS kernel gave up on an internal barrier (every count is 0)
+ * Processing order inside a segment: score descending -- with text rounding the ROUNDED score, so scores that print alike tie --
+ * ties in ascending input row (tile order, then the row inside the tile).  numpy's argsort()[::-1] in the reference leaves ties
+ * to its sort; where a segment has none, text rounding gives the file pipeline's result bit for bit.  Without it the rows
+ * keep the full float32 precision: not the file pipeline's result.
+ * All work is plain launches on `stream`; nothing is copied to the host.  1 <= nc <= 256, n, ntile and n_src * nc below 2^31,
+ * else OBB_ERR_BAD_ARG before any device call.  Workspace: obb_tile_merge_workspace_bytes(n, n_src, nc).
+ */
+#define OBB_TILE_MERGE_TEXT_ROUNDING 1
+#define OBB_TILE_MERGE_POLY_ALL 2
+typedef struct obb_tile_rec {
+  int32_t src_image, left, up;
+  double rate;
+  float pad_x, pad_y, gain;
+} obb_tile_rec;
+size_t obb_tile_merge_workspace_bytes(int64_t n, int64_t n_src, int64_t nc);
+int obb_tile_merge_f32(const float* det7, const int64_t* det_off_host, const obb_tile_rec* tiles_host, int64_t ntile, int64_t n_src,
+                       int64_t nc, double thresh, int flags, double* out, int64_t* out_count, int32_t* info, void* ws, size_t ws_len,
+                       void* stream);
+
+/*
  * DOTA Task-1 evaluation: the detection x ground-truth part of voc_eval (DOTA_devkit/dota_evaluation_task1.py:168-223)
  * for all detections of a class file in one call.  Per detection, over the ground-truth quads of its own image: the
  * horizontal-box gate with the +1 convention (:181-204), iou_poly(GT, det) of DOTA_devkit/polyiou.cpp in IEEE double for

@@ -202,15 +202,20 @@ def parse_result_table(fullname):
     return ResultTable(text, names, group[:n].copy(), dets[:n].copy(), name_off[:n].copy(), name_len[:n].copy())
 
 
-def format_result_rows(names, dets):
-    """format_result_line for many rows at once (native): names per row, dets (n, 9)."""
+def format_result_text(names, dets):
+    """format_result_line for many rows at once (native): names per row, dets (n, 9) -> the lines as one bytes object."""
     blob = ' '.join(names).encode()
     lens = np.array([len(x.encode()) for x in names], dtype=np.int32)
     offs = np.zeros(len(names), dtype=np.int32)
     if len(names) > 1:
         offs[1:] = np.cumsum(lens[:-1] + 1)
     t = ResultTable(blob, None, None, np.ascontiguousarray(dets, dtype=np.float64), offs, lens)
-    return t.format_rows(np.arange(len(names))).decode().splitlines()
+    return t.format_rows(np.arange(len(names)))
+
+
+def format_result_rows(names, dets):
+    """format_result_text as a list of lines."""
+    return format_result_text(names, dets).decode().splitlines()
 
 
 def mergesingle(dstpath, nms, fullname):

@@ -39,6 +39,8 @@ SIGNATURES = {
     "obb_merge_nms_poly_f64": (_i32, [_vp, _i64, _vp, _vp, _i64, C.c_double, _vp, _vp, _vp, _sz, _vp]),
     "obb_merge_nms_poly_all_f64": (_i32, [_vp, _i64, _vp, _vp, _i64, C.c_double, _vp, _vp, _vp, _sz, _vp]),
     "obb_merge_nms_hbb_f64": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "obb_tile_merge_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "obb_tile_merge_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_double, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),      # tiles: TileRec array (tile_merge.py)
     "obb_task1_parse_tiles": (_i64, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "obb_task1_format_rows": (_i64, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64]),
     "obb_task1_parse_dets": (_i64, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),

@@ -19,6 +19,7 @@
 #include "detect_math.h"
 #include "confusion_math.h"
 #include "geom.h"
+#include "valpost_device.h"
 #include "ws_layout.h"
 
 namespace obb {
@@ -494,13 +495,8 @@ namespace obb {
 //   pred_polyn (n,10) = scale_polys(pred_poly): (x - pad_x) / gain, (y - pad_y) / gain     native image space
 //   pred_hbbn  (n,6)  = [xywh2xyxy(poly2hbb(polyn)), conf, cls]
 // (utils/rboxs_utils.py:106-181, utils/general.py:590-597 xywh2xyxy, :636-650 scale_polys)
-// corners of one rbox (utils/rboxs_utils.py:106-145) and the horizontal box around 8 coordinates (poly2hbb + xywh2xyxy)
-__device__ __forceinline__ void vt_rbox2poly(float x, float y, float w, float h, float th, float* p) {
-  const float Cos = cosf(th), Sin = sinf(th);
-  const float v1x = w / 2 * Cos, v1y = -w / 2 * Sin, v2x = -h / 2 * Sin, v2y = -h / 2 * Cos;
-  p[0] = x + v1x + v2x; p[1] = y + v1y + v2y; p[2] = x + v1x - v2x; p[3] = y + v1y - v2y;
-  p[4] = x - v1x - v2x; p[5] = y - v1y - v2y; p[6] = x - v1x + v2x; p[7] = y - v1y + v2y;
-}
+// corners of one rbox and scale_polys: valpost_device.h (vt_rbox2poly, vt_scale_poly); the horizontal box around 8 coordinates
+// (poly2hbb + xywh2xyxy):
 __device__ __forceinline__ void vt_hbb_xyxy(const float* q, float* o) {
   const float xmax = fmaxf(fmaxf(q[0], q[2]), fmaxf(q[4], q[6])), xmin = fminf(fminf(q[0], q[2]), fminf(q[4], q[6]));
   const float ymax = fmaxf(fmaxf(q[1], q[3]), fmaxf(q[5], q[7])), ymin = fminf(fminf(q[1], q[3]), fminf(q[5], q[7]));
@@ -517,8 +513,7 @@ __device__ __forceinline__ void vt_post_one(const float* __restrict__ r, long lo
   if (poly10) { for (int k = 0; k < 8; k++) poly10[i * 10 + k] = p[k]; poly10[i * 10 + 8] = conf; poly10[i * 10 + 9] = cls; }
   if (hbb6) { vt_hbb_xyxy(p, o4); for (int k = 0; k < 4; k++) hbb6[i * 6 + k] = o4[k]; hbb6[i * 6 + 4] = conf; hbb6[i * 6 + 5] = cls; }
   float pn[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) pn[k] = (p[k] - ((k & 1) ? pad_y : pad_x)) / gain;
+  vt_scale_poly(p, pad_x, pad_y, gain, pn);
   if (polyn10) { for (int k = 0; k < 8; k++) polyn10[i * 10 + k] = pn[k]; polyn10[i * 10 + 8] = conf; polyn10[i * 10 + 9] = cls; }
   vt_hbb_xyxy(pn, o4n);
   if (hbbn6) { for (int k = 0; k < 4; k++) hbbn6[i * 6 + k] = o4n[k]; hbbn6[i * 6 + 4] = conf; hbbn6[i * 6 + 5] = cls; }

@@ -7,14 +7,15 @@
 // Launch chain (no exchange between workgroups inside a launch, guide Guideline 16):
 //   k_ap_keys / k_ap_labels   keys + LDS class histograms (one atomic per workgroup and class), flags, true positives at column 0
 //   k_ap_tables               segment offsets per class; tiles of kApTile rows that never straddle a class
-//   k_ap_bitonic(_lds)        bitonic network with every comparator pointing up: rows >= n act as +inf and are never touched;
-//                             the steps inside blocks of 2048 rows run in LDS, the wider ones one launch each
+//   bitonic_sort_pairs        (bitonic_sort.h) bitonic network with every comparator pointing up: rows >= n act as +inf and are
+//                             never touched; the steps inside blocks of 2048 rows run in LDS, the wider ones one launch each
 //   k_ap_tile_sum -> k_ap_class_scan -> k_ap_tile_tpc      prefix sums of `correct` (integers): reduce, scan of totals, apply
 //   k_ap_class_rmax -> k_ap_tile_env                        reverse running maximum of precision: scan of tile maxima, apply
 //   k_ap_ap, k_ap_pr, k_ap_best                             101 / 1000 binary searches per curve, trapezoid, F1, best index
 #include <hip/hip_runtime.h>
 
 #include "ap_math.h"
+#include "bitonic_sort.h"
 #include "obb_hip.h"
 #include "ws_layout.h"
 
@@ -129,69 +130,6 @@ __global__ void k_ap_tables(const int* __restrict__ counts, int nc_max, int* __r
   }
   seg_off[nc_max] = rows;
   tile_start[nc_max] = tiles;
-}
-
-// one comparator per row i with its partner above it; mirror: the first step of a merge of blocks of k rows
-__global__ __launch_bounds__(kApThreads) void k_ap_bitonic(unsigned long long* __restrict__ key, int* __restrict__ idx, unsigned n, unsigned k,
-                                                            unsigned j, int mirror) {
-  const unsigned i = blockIdx.x * (unsigned)kApThreads + threadIdx.x;
-  if (i >= n) return;
-  const unsigned p = mirror ? (i ^ (k - 1u)) : (i ^ j);
-  if (p <= i || p >= n) return;
-  const unsigned long long ka = key[i], kb = key[p];
-  const int ia = idx[i], ib = idx[p];
-  if (kb < ka || (kb == ka && ib < ia)) {
-    key[i] = kb, key[p] = ka;
-    idx[i] = ib, idx[p] = ia;
-  }
-}
-
-// The steps whose partner lies inside a block of kApSortBlock rows run in LDS: one launch for the stages k = 2 .. kApSortBlock
-// (merge_only = 0), one per later stage for its steps j = kApSortBlock / 2 .. 1 (merge_only = 1).  Rows >= n are +inf there too.
-constexpr int kApSortBlock = 2048;      // 24 KiB of LDS: 2048 x (8-byte key, 4-byte row index)
-
-__device__ __forceinline__ void lds_cmpx(unsigned long long* sk, int* si, int i, int p) {
-  const unsigned long long ka = sk[i], kb = sk[p];
-  const int ia = si[i], ib = si[p];
-  if (kb < ka || (kb == ka && ib < ia)) {
-    sk[i] = kb, sk[p] = ka;
-    si[i] = ib, si[p] = ia;
-  }
-}
-
-__global__ __launch_bounds__(kApThreads) void k_ap_bitonic_lds(unsigned long long* __restrict__ key, int* __restrict__ idx, unsigned n,
-                                                                int merge_only) {
-  __shared__ unsigned long long sk[kApSortBlock];
-  __shared__ int si[kApSortBlock];
-  const int tid = threadIdx.x;
-  const unsigned base = blockIdx.x * (unsigned)kApSortBlock;
-  for (int q = tid; q < kApSortBlock; q += kApThreads) {
-    const unsigned g = base + (unsigned)q;
-    sk[q] = g < n ? key[g] : ~0ull;
-    si[q] = g < n ? idx[g] : 0x7fffffff;
-  }
-  __syncthreads();
-  for (int k = merge_only ? kApSortBlock : 2; k <= kApSortBlock; k <<= 1) {
-    if (!merge_only) {                                   // mirror step of the merge of blocks of k rows
-      const int h = k >> 1;
-      for (int t = tid; t < kApSortBlock / 2; t += kApThreads) {
-        const int i = ((t & ~(h - 1)) << 1) | (t & (h - 1));
-        lds_cmpx(sk, si, i, i ^ (k - 1));
-      }
-      __syncthreads();
-    }
-    for (int j = merge_only ? k >> 1 : k >> 2; j > 0; j >>= 1) {
-      for (int t = tid; t < kApSortBlock / 2; t += kApThreads) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        lds_cmpx(sk, si, i, i + j);
-      }
-      __syncthreads();
-    }
-  }
-  for (int q = tid; q < kApSortBlock; q += kApThreads) {
-    const unsigned g = base + (unsigned)q;
-    if (g < n) key[g] = sk[q], idx[g] = si[q];
-  }
 }
 
 struct Tile {
@@ -462,14 +400,7 @@ int obb_ap_per_class_f32(const float* stats, int64_t row_stride, int64_t n, int 
     const unsigned tiles = rows / kApTile + (unsigned)nc_max;      // >= the number of class-aligned tiles
     k_ap_keys<<<grid, kApThreads, 0, st>>>(stats, row_stride, (int)n, niou, nc_max, w.key, w.idx, counts, info);
     k_ap_tables<<<1, 64, 0, st>>>(counts, nc_max, w.seg_off, w.tile_start);
-    const unsigned sort_blocks = (rows + kApSortBlock - 1) / kApSortBlock;
-    k_ap_bitonic_lds<<<sort_blocks, kApThreads, 0, st>>>(w.key, w.idx, rows, 0);
-    for (unsigned long long k = 2ull * kApSortBlock; (k >> 1) < rows; k <<= 1) {
-      k_ap_bitonic<<<grid, kApThreads, 0, st>>>(w.key, w.idx, rows, (unsigned)k, 0u, 1);
-      for (unsigned j = (unsigned)(k >> 2); j >= (unsigned)kApSortBlock; j >>= 1)
-        k_ap_bitonic<<<grid, kApThreads, 0, st>>>(w.key, w.idx, rows, (unsigned)k, j, 0);
-      k_ap_bitonic_lds<<<sort_blocks, kApThreads, 0, st>>>(w.key, w.idx, rows, 1);
-    }
+    bitonic_sort_pairs(w.key, w.idx, rows, st);
     k_ap_tile_sum<<<tiles, kApThreads, 0, st>>>(stats, row_stride, niou, nc_max, w.idx, w.seg_off, w.tile_start, w.tile_tp);
     k_ap_class_scan<<<nc_max, 64, 0, st>>>(niou, w.tile_start, w.tile_tp);
     k_ap_tile_tpc<<<tiles, kApThreads, 0, st>>>(stats, row_stride, niou, nc_max, w.idx, w.seg_off, w.tile_start, w.tile_tp, w.tpc, w.tile_max);

@@ -1,4 +1,5 @@
-// Rotated / quad NMS entry points (C ABI) and nothing else: the single-list and merge drivers are in nms_single.h, the fused
+// Rotated / quad NMS entry points (C ABI) and nothing else: the single-list and merge drivers are in nms_single.h, the merge's
+// device front in tile_merge.h, the fused
 // non_max_suppression_obb driver in nmsobb_impl.h (fronts: nmsobb_front.h, nms_head.h), what they share in nms_driver.h.
 //
 // Replaces, on device tensors:
@@ -21,6 +22,7 @@
 #include "nmsobb_hints.h"
 #include "nmsobb_impl.h"
 #include "obb_hip.h"
+#include "tile_merge.h"
 #include "tta_head_plan.h"
 
 using namespace obb;
@@ -64,6 +66,18 @@ int obb_merge_nms_hbb_f64(const double* dets, int64_t row_stride, int64_t n, con
                           double thresh, int64_t* keep_out, int64_t* num_keep, void* ws, size_t ws_bytes, void* stream) {
   if (row_stride < 4 || row_stride > 0x7fffffff) return OBB_ERR_BAD_ARG;
   return run_merge_nms(5, dets, (int)row_stride, n, order, seg_off, nseg, thresh, keep_out, num_keep, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// the device front of the merge (tile_merge.h): per-tile NMS outputs in, merged full-image detections out
+size_t obb_tile_merge_workspace_bytes(int64_t n, int64_t n_src, int64_t nc) {
+  if (n < 0 || n > 0x7fffffffLL || n_src < 1 || n_src > 0x7fffffffLL || nc < 1 || nc > kTmMaxNc || n_src * nc > 0x7fffffffLL) return 0;
+  return tm_layout(nullptr, n, n_src * nc, 2, device_cus().cus).bytes;      // (both variants: one record layout, QuadGeom64)
+}
+
+int obb_tile_merge_f32(const float* det7, const int64_t* det_off_host, const obb_tile_rec* tiles_host, int64_t ntile, int64_t n_src,
+                       int64_t nc, double thresh, int flags, double* out, int64_t* out_count, int32_t* info, void* ws, size_t ws_len,
+                       void* stream) {
+  return run_tile_merge(det7, det_off_host, tiles_host, ntile, n_src, nc, thresh, flags, out, out_count, info, ws, ws_len, (hipStream_t)stream);
 }
 
 // Devkit host-pointer API (DOTA_devkit/poly_nms_gpu/poly_nms.hpp:9-10, poly_nms_kernel.cu:277-329): the rows
