@@ -744,6 +744,35 @@ int obb_ap_per_class_f32(const float* stats, int64_t row_stride, int64_t n, int 
                          double* ap, double* prf, int32_t* counts, int32_t* info, double* curves, void* ws, size_t ws_bytes,
                          void* stream);
 
+/*
+ * Merge of the validation statistics of several ranks into GLOBAL IMAGE ORDER (csrc/stats_merge.h): sharded validation gives
+ * every rank the rows of its own images, image after image; ap_per_class orders equal confidences by ascending row index of the
+ * rows in image order, so the ranks' rows must be interleaved image by image, not concatenated rank by rank.
+ *   src                  one device buffer of `world` runs: run r starts at row r * run_stride and holds rows_per_run_host[r]
+ *                        (<= run_stride) rows of src_stride >= width floats, the images of the run back to back
+ *   counts, img_id       (world, max_images_per_run) int32 / int64 device, rank-major: rows and global id of the j-th image of run r
+ *                        at [r * max_images_per_run + j], j < images_per_run_host[r] (<= max_images_per_run); the padding is not read
+ *   n_images_total       ids are 0 .. n_images_total - 1; an id no run supplies is an image with no rows
+ *   dst                  dst_rows rows of dst_stride >= width floats: image 0's rows, image 1's rows, ...; the first `width` floats
+ *                        of the first info[1] rows are written and NOTHING else (not the gap of a wider stride, not a row behind)
+ *   counts_out           (n_images_total) int32 device or NULL: rows of every image, by id
+ *   info                 (4) int32 device.  [1] the total number of rows.  [0] != 0: the call copied NOTHING, dst is as it was:
+ *                        bit 0 an id outside [0, n_images_total); bit 1 an id supplied twice ([2] is one such id); bit 2 the counts
+ *                        of a run do not add up to rows_per_run_host[r], or one is negative ([3] is one such run); bit 3 the
+ *                        total exceeds dst_rows
+ * The same entry merges the rows and the oriented-box rows (width niou + 2) and, with the per-image LABEL counts, target_cls
+ * (width 1).  Plain launches on `stream`, nothing is read back; the copy runs one wave per image with its lanes along the
+ * image's contiguous floats.  Before any device call: OBB_ERR_BAD_ARG for a NULL info / host array (src, counts, img_id, dst when
+ * there is something to read or write), world < 1, width < 1, a stride < width, a run longer than run_stride, more images in a run
+ * than max_images_per_run, n_images_total or the rows of all runs >= 2^31 - 1; OBB_ERR_WORKSPACE for a NULL, misaligned or short
+ * ws (obb_stats_merge_workspace_bytes(n_images_total), linear in it).
+ */
+size_t obb_stats_merge_workspace_bytes(int64_t n_images_total);
+int obb_stats_merge_f32(const float* src, int64_t src_stride, int64_t run_stride, const int64_t* rows_per_run_host, const int32_t* counts,
+                        const int64_t* img_id, int64_t max_images_per_run, const int64_t* images_per_run_host, int64_t world,
+                        int64_t n_images_total, int64_t width, float* dst, int64_t dst_stride, int64_t dst_rows, int32_t* counts_out,
+                        int32_t* info, void* ws, size_t ws_cap, void* stream);
+
 /* ------------------------------------------------------------------ pairwise IoU --------------------- */
 
 /* out[i] = IoU(a5[i], b5[i]); the device function behind the NMS

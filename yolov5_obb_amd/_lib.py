@@ -88,6 +88,8 @@ SIGNATURES = {
     "obb_confusion_process_batch_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _sz, _vp]),
     "obb_ap_per_class_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "obb_ap_per_class_f32": (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "obb_stats_merge_workspace_bytes": (_sz, [_i64]),
+    "obb_stats_merge_f32": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "obb_rotated_iou_pairs_f32": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "obb_rotated_iou_matrix_f32": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "obb_quad_iou_matrix_f32": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),

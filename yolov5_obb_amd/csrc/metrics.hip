@@ -17,6 +17,7 @@
 #include "ap_math.h"
 #include "bitonic_sort.h"
 #include "obb_hip.h"
+#include "stats_merge.h"
 #include "ws_layout.h"
 
 namespace obb {
@@ -412,6 +413,19 @@ int obb_ap_per_class_f32(const float* stats, int64_t row_stride, int64_t n, int 
   }
   k_ap_best<<<1, 1024, 0, st>>>(nc_max, counts, cur, prf, info);
   return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
+}
+
+size_t obb_stats_merge_workspace_bytes(int64_t n_images_total) {
+  if (n_images_total < 0 || n_images_total >= 0x7fffffffLL) return 0;
+  return obb::sm_layout(nullptr, n_images_total).bytes;
+}
+
+int obb_stats_merge_f32(const float* src, int64_t src_stride, int64_t run_stride, const int64_t* rows_per_run_host, const int32_t* counts,
+                        const int64_t* img_id, int64_t max_images_per_run, const int64_t* images_per_run_host, int64_t world,
+                        int64_t n_images_total, int64_t width, float* dst, int64_t dst_stride, int64_t dst_rows, int32_t* counts_out,
+                        int32_t* info, void* ws, size_t ws_cap, void* stream) {
+  return obb::run_stats_merge(src, src_stride, run_stride, rows_per_run_host, counts, img_id, max_images_per_run, images_per_run_host, world,
+                              n_images_total, width, dst, dst_stride, dst_rows, counts_out, info, ws, ws_cap, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -187,6 +187,26 @@ class ConfusionMatrix:
             for ch in tb.chunks(shapes):
                 self._launch(L, tb, ch, st)
 
+    def all_reduce(self, group=None, device=None):
+        """Sum the counters over the ranks of a process group (the cells AND the counter of classes out of range): after it every
+        rank holds the matrix of the whole run.  RCCL reduces the device array in place; any other backend stages it through the
+        host.  device: where the counters are made when this rank has not seen a batch.  No process group: nothing to do."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return
+        if self._mat is None:
+            dev = self.device if self.device is not None else device
+            if dev is None:
+                raise RuntimeError("ConfusionMatrix.all_reduce: no batch was added on this rank; pass device=")
+            dev = torch.device(dev)
+            self._counters(dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device()))
+        if dist.get_backend(group) == "nccl":
+            dist.all_reduce(self._mat, group=group)
+        else:
+            host = self._mat.cpu()
+            dist.all_reduce(host, group=group)
+            self._mat.copy_(host)
+
     @property
     def matrix(self):
         """(nc + 1, nc + 1) float64 numpy array [predicted][true], as the reference's attribute.  The one place that waits for

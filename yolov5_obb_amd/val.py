@@ -6,7 +6,7 @@ import threading
 
 import torch
 
-from . import _lib
+from . import _lib, stats_merge
 from .tail_batch import MAX_BS, TailBatch, as_f32, box_arrays, split_rows
 
 
@@ -197,7 +197,11 @@ class ValStats:
     """The statistics of a whole validation run in DEVICE memory: what val.py:250 appends per image and :269 concatenates, as
     one (n, niou + 2) array of rows [correct x niou as 0 / 1, conf, cls] (the rows obb_val_tail_batch_f32 writes, in the order
     of the images) plus the class of every label -- the inputs of utils.metrics.ap_per_class, which then runs on them where
-    they lie.  Nothing is copied to the host and nothing waits for the stream until ap_per_class() / cpu() is called."""
+    they lie.  Nothing is copied to the host and nothing waits for the stream until ap_per_class() / cpu() is called.
+
+    Beside the rows, three values per image seen, on the device too: its rows, its labels and a global image id (`image_ids=` of
+    add_batch; a running index by default).  They are what puts the statistics of several ranks back in image order: merged()
+    for accumulators on one device, all_gather() across the ranks of a process group (stats_merge.py)."""
 
     def __init__(self, niou=10, device=None, capacity=1 << 16, obb=False):
         self.niou = int(niou)
@@ -212,6 +216,13 @@ class ValStats:
         # obb=True: the same rows with process_batch on the ROTATED boxes (obb_val_tail_batch_obb_f32), row for row beside the others
         self._rows_obb = torch.empty_like(self._rows) if self.obb else None
         self._match = None
+        self.k = 0                             # images seen
+        self._img_rows = torch.empty(1024, dtype=torch.int32, device=self.device)
+        self._img_labels = torch.empty(1024, dtype=torch.int32, device=self.device)
+        self._img_ids = torch.empty(1024, dtype=torch.int64, device=self.device)
+        self._arange = {}                      # batch size -> (1, bs) float32 0 .. bs - 1 on the device
+        self._merge_info, self._merge_error = None, None
+        self.supplied = None                   # merged() / all_gather(): the images their parts held between them
 
     @property
     def rows(self):
@@ -232,11 +243,41 @@ class ValStats:
         new[:used] = buf[:used]
         return new
 
-    def add_batch(self, preds, targets, shapes, iouv, want_boxes=False, confusion=None):
+    def _note_images(self, tb, image_ids):
+        """Rows, labels and id of every image of the batch, behind the ones already held.  Nothing waits: the row counts and the
+        ids are on the host already (one pinned array, one asynchronous copy), the label counts are a compare-and-sum over the
+        image column of `targets` on the stream (an image index outside the batch counts nowhere and indexes nothing)."""
+        bs, k = tb.bs, self.k
+        if bs == 0:
+            return
+        ids = range(k, k + bs) if image_ids is None else [int(i) for i in image_ids]
+        if len(ids) != bs:
+            raise RuntimeError(f"ValStats: {len(ids)} image ids for a batch of {bs} images")
+        host = torch.tensor(tb.counts + list(ids), dtype=torch.int64).pin_memory()
+        both = host.to(self.device, non_blocking=True)
+        self._img_rows = self._grown(self._img_rows, k, k + bs)
+        self._img_labels = self._grown(self._img_labels, k, k + bs)
+        self._img_ids = self._grown(self._img_ids, k, k + bs)
+        self._img_rows[k:k + bs] = both[:bs]
+        self._img_ids[k:k + bs] = both[bs:]
+        if tb.nt:
+            ar = self._arange.get(bs)
+            if ar is None:
+                ar = self._arange[bs] = torch.arange(bs, dtype=torch.float32, device=self.device)[None, :]
+            self._img_labels[k:k + bs] = (tb.tg[:, 0:1] == ar).sum(0)
+        else:
+            self._img_labels[k:k + bs] = 0
+        self.k += bs
+
+    def add_batch(self, preds, targets, shapes, iouv, want_boxes=False, confusion=None, image_ids=None):
         """The inputs of val_tail_batch; the rows go straight behind the ones already held.  Returns None, or with want_boxes
         the packed device arrays (pred_poly, pred_hbb, pred_polyn, pred_hbbn) and the per-image offsets.
         confusion: a utils.metrics.ConfusionMatrix -- val.py:245-246 with plots=True: its launch runs right behind the tail's
-        two, on the same packed detections and targets."""
+        two, on the same packed detections and targets.
+        image_ids: the global id of every image of the batch (a sharded run: its index in the whole image list); default: the
+        running index 0, 1, 2, ... of the images this accumulator has seen.  Images without detections, without labels or with
+        neither are recorded too.  (merged() / all_gather() take the labels of an image to be consecutive rows of `targets`, the
+        images ascending, as collate_fn yields them.)"""
         dev = self.device
         if int(iouv.shape[0]) != self.niou:
             raise RuntimeError(f"ValStats: iouv has {int(iouv.shape[0])} levels, this accumulator {self.niou}")
@@ -247,6 +288,7 @@ class ValStats:
         tb = TailBatch(preds, targets, dev)
         n, nt = tb.n, tb.nt
         self._result = [None, None]
+        self._note_images(tb, image_ids)
         if nt:
             self._tcls = self._grown(self._tcls, self.m, self.m + nt)
             self._tcls[self.m:self.m + nt] = tb.tg[:, 1]
@@ -277,6 +319,7 @@ class ValStats:
 
     def _metrics(self, obb=False):
         """(the 7-tuple of ap_per_class, info) over `rows`, or over `rows_obb`; kept until the next batch."""
+        self._check_merge()
         rows = self.rows_obb if obb else self.rows
         if self._result[obb] is None:
             from .utils import metrics
@@ -284,6 +327,7 @@ class ValStats:
         return self._result[obb]
 
     def _cpu(self, rows):
+        self._check_merge()
         arr = rows.cpu().numpy()
         return arr[:, :self.niou] > 0.5, arr[:, self.niou].copy(), arr[:, self.niou + 1].copy(), self.target_cls.cpu().numpy()
 
@@ -299,6 +343,74 @@ class ValStats:
     def cpu(self):
         """(correct bool (n, niou), conf (n), pcls (n), tcls (m)) numpy arrays: the four arrays of val.py:269."""
         return self._cpu(self.rows)
+
+    # ---- per image: rows, labels, global id -- and the merge of several accumulators in id order
+    @property
+    def img_rows(self):
+        """(k) int32 on the device: the detection rows of every image seen, in the order they were added."""
+        return self._img_rows[:self.k]
+
+    @property
+    def img_labels(self):
+        """(k) int32 on the device: the labels of every image seen."""
+        return self._img_labels[:self.k]
+
+    @property
+    def img_ids(self):
+        """(k) int64 on the device: the global id of every image seen."""
+        return self._img_ids[:self.k]
+
+    def _shard(self):
+        return stats_merge.Shard(self.rows, self._rows_obb[:self.n] if self.obb else None, self.target_cls, self.img_rows, self.img_labels,
+                                 self.img_ids)
+
+    @classmethod
+    def _of_merged(cls, mg, niou, obb, device):
+        out = cls(niou=niou, device=device, capacity=1, obb=obb)
+        out._rows, out._rows_obb, out._tcls = mg.rows, mg.rows_obb, mg.tcls
+        out.n, out.m, out.k = mg.totals
+        out._img_rows, out._img_labels = mg.img_rows, mg.img_labels
+        out._img_ids = torch.arange(out.k, dtype=torch.int64, device=out.device)
+        out._merge_info = mg.info
+        out.supplied = mg.supplied             # images the merged parts held between them (k counts the ids no part held too)
+        return out
+
+    def _check_merge(self):
+        """The info words of the merge that made this accumulator, read where the caller synchronises anyway."""
+        if self._merge_info is not None:
+            self._merge_error = stats_merge.describe(self._merge_info.cpu())
+            self._merge_info = None
+        if self._merge_error:
+            raise RuntimeError(f"ValStats: {self._merge_error}")
+
+    @classmethod
+    def merged(cls, parts, n_images_total=None, merge=None):
+        """parts: accumulators on ONE device (virtual ranks, or shards gathered there) whose image ids are distinct -> a new
+        ValStats whose rows, rows_obb, target_cls, per-image counts and ids are those of a single accumulator that was fed every
+        image in ascending id order (ids no part holds, below n_images_total, are images without rows and labels).
+        n_images_total: default the number of images the parts hold.  Three calls of obb_stats_merge_f32, nothing waits; an id
+        held twice, an id outside [0, n_images_total) or counts that do not add up raise RuntimeError at the next
+        ap_per_class() / cpu(), where the host waits for the device anyway."""
+        parts = list(parts)
+        if not parts:
+            raise RuntimeError("ValStats.merged: no accumulators")
+        p0 = parts[0]
+        for p in parts:
+            if p.device != p0.device or p.niou != p0.niou or p.obb != p0.obb:
+                raise RuntimeError("ValStats.merged: the accumulators must share device, niou and obb")
+            p._check_merge()
+        with _lib.guard(p0.device):
+            mg = stats_merge.merge_parts([p._shard() for p in parts], p0.niou + 2, p0.obb, n_images_total, merge)
+        return cls._of_merged(mg, p0.niou, p0.obb, p0.device)
+
+    def all_gather(self, group=None, n_images_total=None, merge=None):
+        """The one exchange of a sharded run (stats_merge.exchange): the totals of every rank, then the padded rows -- RCCL
+        gathers device buffers, any other backend stages through the host, once per run -- then merged() on every rank: each
+        rank returns the ValStats of the whole run.  Without a process group: merged([self])."""
+        self._check_merge()
+        with _lib.guard(self.device):
+            mg = stats_merge.exchange(self._shard(), self.niou + 2, self.obb, group, n_images_total, merge)
+        return self._of_merged(mg, self.niou, self.obb, self.device)
 
     # ---- obb=True: the oriented-box statistics, accessor for accessor
     def _need_obb(self):

@@ -52,13 +52,17 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
     (whole job), stats (rank 0: the four concatenated arrays in original image order), metrics (rank 0: what
     ap_per_class returned, or None).  collect=False: no exchange at all -- the rank's own seen / dt (a caller that only wants
     the time buckets and does its own reduction, bench.py).
-    device_metrics=True (CUDA, one process, the HIP tail): the statistics stay in device memory (val.ValStats) and the metrics
+    device_metrics=True (CUDA, the HIP tail): the statistics stay in device memory (val.ValStats) and the metrics
     are this package's utils.metrics.ap_per_class over them -- ties among equal confidences by ascending row index, where the
     reference's numpy leaves them unspecified; `ap_per_class` is not called, "stats" stays None, "val_stats" is the accumulator
-    and "metrics" its 7-tuple, or None when nothing matched (val.py:270).
+    and "metrics" its 7-tuple, or None when nothing matched (val.py:270).  On more than one rank every batch carries the global
+    ids of its images (loader.global_indices, or the strided split), and after the loop ValStats.all_gather() -- the one
+    exchange -- puts the rows of all ranks in image order on the device (stats_merge.py): EVERY rank computes and returns the
+    metrics of the whole run, bit for bit those of one process; "val_stats" is the merged accumulator, "seen" the images of all
+    ranks, "dt" the slowest rank's.
     confusion_matrix (with device_metrics=True): a utils.metrics.ConfusionMatrix that every batch is added to on the device
-    (val.py:245-246 with plots=True); it comes back as "confusion_matrix".  One process only: its counters are plain sums that a
-    later change can all-reduce.
+    (val.py:245-246 with plots=True); it comes back as "confusion_matrix".  On more than one rank its counters are summed over
+    the ranks after the loop (ConfusionMatrix.all_reduce): every rank holds the matrix of the whole run.
     obb_metrics=True (with device_metrics=True): every batch also goes through the oriented-box tail (val.ValStats(obb=True):
     process_batch with the rotated IoU), and "metrics_obb" is the same 7-tuple over those rows -- the OBB mAP@0.5 and
     mAP@0.5:0.95 beside the horizontal ones -- or None when nothing matched."""
@@ -82,19 +86,13 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
     iouv = torch.linspace(0.5, 0.95, niou, device=device)           # val.py:172
     vstats = None
     if device_metrics:
-        if world > 1:
-            # a stable tie order across ranks needs a global (image, row) key carried with every row
-            raise RuntimeError("val_sharded.run: device_metrics=True needs a single process (world size 1)")
         if batch_tail is None or device.type != "cuda":
             raise RuntimeError("val_sharded.run: device_metrics=True needs a CUDA device and this package's own tail")
         vstats = V.ValStats(niou=niou, device=device, obb=bool(obb_metrics))
     elif obb_metrics:
         raise RuntimeError("val_sharded.run: obb_metrics needs device_metrics=True")
-    if confusion_matrix is not None:
-        if world > 1:
-            raise RuntimeError("val_sharded.run: confusion_matrix needs a single process (world size 1)")
-        if vstats is None:
-            raise RuntimeError("val_sharded.run: confusion_matrix needs device_metrics=True")
+    if confusion_matrix is not None and vstats is None:
+        raise RuntimeError("val_sharded.run: confusion_matrix needs device_metrics=True")
     gidx = getattr(loader, "global_indices", None)
     per_image, dt, seen = [], [0.0, 0.0, 0.0], 0
     dt_batches = []                                                  # (pre-process, inference, NMS) seconds of every batch
@@ -120,7 +118,10 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
                     for pred in out:
                         pred[:, 6] = 0
                 if vstats is not None:
-                    vstats.add_batch(out, targets, shapes, iouv, confusion=confusion_matrix)      # rows and label classes stay on the device
+                    ids = None                                       # (one process: the accumulator's own running index)
+                    if world > 1:                                    # the images' places in the whole list: the key of the merge
+                        ids = gidx[seen:seen + len(out)] if gidx is not None else range(rank + world * seen, rank + world * (seen + len(out)), world)
+                    vstats.add_batch(out, targets, shapes, iouv, confusion=confusion_matrix, image_ids=ids)      # rows and label classes stay on the device
                     seen += len(out)
                     continue
                 tail = batch_tail(out, targets, shapes, iouv)                    # val.py:209-250 for the whole batch
@@ -167,8 +168,18 @@ def run(model, loader, n_total=None, conf_thres=0.001, iou_thres=0.4, half=True,
         return {"rank": rank, "world": world, "seen": seen, "dt": list(dt), "img_per_s": seen / max(sum(dt), 1e-12), "stats": None,
                 "metrics": None, "dt_batches": dt_batches}
     if vstats is not None:
+        dt_all = list(dt)
+        if world > 1:                                                # ---- the one exchange: every rank gets the whole run's statistics
+            vstats = vstats.all_gather(n_images_total=n_total)
+            if confusion_matrix is not None:
+                confusion_matrix.all_reduce(device=device)
+            import torch.distributed as dist
+            seen = vstats.supplied                                   # the sum over ranks, as on the host path
+            if n_total is not None and seen != int(n_total):
+                raise RuntimeError(f"{int(n_total) - seen} items missing after the gather")
+            dt_all = [shard.max_over_ranks(x, device=device if dist.get_backend() == "nccl" else None) for x in dt]
         metrics = vstats.ap_per_class()
-        res = {"rank": rank, "world": world, "seen": seen, "dt": list(dt), "img_per_s": seen / max(sum(dt), 1e-12), "stats": None,
+        res = {"rank": rank, "world": world, "seen": seen, "dt": dt_all, "img_per_s": seen / max(sum(dt_all), 1e-12), "stats": None,
                "metrics": metrics if vstats.any_tp else None, "dt_batches": dt_batches, "val_stats": vstats}
         if confusion_matrix is not None:
             res["confusion_matrix"] = confusion_matrix
