@@ -228,6 +228,39 @@ int obb_eval_best_gt_f64(const double* dets8, const int32_t* det_img, int64_t nd
                          int64_t n_img, double* ovmax, int32_t* jmax, void* stream);
 
 /*
+ * In-memory DOTA Task-1 evaluation: the whole of voc_eval (DOTA_devkit/dota_evaluation_task1.py:88-249) for every class in one
+ * launch chain -- merged full-image rows and a resident ground-truth set in, per-class AP out (csrc/task1_eval.h; the arithmetic of
+ * the curve, of voc_ap and of its np.sum is csrc/voc_ap_math.h, IEEE double in numpy's order).
+ *   dets      nd rows of det_stride >= 11 doubles, the layout obb_tile_merge_f32 writes: [x1 y1 .. x4 y4, score, cls, src_image]
+ *             (a slice of its `out` is passed as it is); rows are evaluated with the values they carry
+ *   gts8      (ng, 8) doubles grouped by segment cls * n_img + img     gt_off (nc * n_img + 1) int32, ascending, [last] = ng
+ *   difficult (ng) uint8: a hit on such a record is neither TP nor FP, and npos does not count it
+ *   ovthresh  a hit is ovmax > ovthresh (NaN and -inf: no)            flags  OBB_TASK1_EVAL_07_METRIC: the 11-point metric
+ *   ap        (nc) doubles; a class without detections evaluates literally, to 0.0      npos (nc) int64
+ *   cls_off   (nc + 1) int32: class c owns the sorted positions cls_off[c] .. cls_off[c + 1]
+ *   order     (nd) int32 or NULL: the input row at every sorted position
+ *   rec, prec (nd) doubles or NULL: the curves, class after class.  npos == 0 gives NaN or inf recalls as numpy does; a NaN is
+ *             the canonical quiet NaN (payload and sign are not numpy's), every other value has the reference's bits
+ *   info      (2) int32: [0] != 0: some row's class is not an integer in [0, nc) or its image not one in [0, n_img) (the reference
+ *             raises KeyError for an unlisted image); such a row is counted in segment 0, nothing is read out of bounds, the result
+ *             is invalid.  [1]: reserved, 0
+ * Order inside a class: score descending, NaN scores last, -0.0 and +0.0 one value (np.argsort(-confidence)); equal scores in
+ * ascending input row (the package's pinned tie rule; the reference leaves ties to numpy's unstable sort).  A record is claimed by
+ * the lowest sorted position that hits it (an atomic minimum per record: independent of the order the atomics land in).
+ * All work is plain launches on `stream`; nothing is copied to the host, nothing waits.  OBB_ERR_BAD_ARG before any device call
+ * for det_stride < 11, nc outside 1..256, a negative count, nd, ng or nc * n_img at or above 2^31, unknown flags or a NULL
+ * required pointer (dets with nd > 0; gts8, difficult with ng > 0).  nd == 0: ap = 0, cls_off = 0, npos counted.  The workspace
+ * follows the rules of ws / ws_bytes of the other entries (256-byte aligned, at least obb_task1_eval_workspace_bytes, which is 0
+ * for arguments the entry refuses; OBB_ERR_WORKSPACE before any device call).
+ */
+#define OBB_TASK1_EVAL_07_METRIC 1
+size_t obb_task1_eval_workspace_bytes(int64_t nd, int64_t ng, int64_t n_img, int64_t nc);
+int obb_task1_eval_f64(const double* dets, int64_t det_stride, int64_t nd, const double* gts8, const int32_t* gt_off,
+                       const uint8_t* difficult, int64_t ng, int64_t n_img, int64_t nc, double ovthresh, int flags, double* ap,
+                       int64_t* npos, int32_t* cls_off, int32_t* order, double* rec, double* prec, int32_t* info, void* ws,
+                       size_t ws_extent, void* stream);
+
+/*
  * DOTA Task-2 (horizontal box) evaluation: the same part of DOTA_devkit/dota_evaluation_task2.py's voc_eval (:177-202).
  * Per detection, over the boxes of its own image, in IEEE double and in the reference's expression order:
  *   iw = max(min(gx2, bx2) - max(gx1, bx1) + 1., 0.), ih alike, inters = iw * ih,

@@ -7,7 +7,12 @@ other, so they are one device call per class (`obb_eval_best_gt_f64`); the only 
 claimed once, by the best-scored detection that reaches it (:225-233) -- is a first-occurrence pass over (image, jmax)
 done with numpy.  Text parsing, `np.argsort(-confidence)` (the reference's tie order) and the AP integration stay on the
 host, in double, as in the reference.  GPU only.
+
+`GroundTruth` + `evaluate_rows` are the in-memory form of `evaluate`: the merged rows of tile_merge.merge_tiles / detect_large and a
+ground-truth set that stays on the device go through one launch chain (obb_task1_eval_f64, csrc/task1_eval.h: sort, best ground
+truth, claims, curves and the VOC AP arithmetic) and one small copy back.
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -229,3 +234,136 @@ def evaluate(detpath, annopath, imagesetfile, classnames, ovthresh=0.5, use_07_m
         classaps.append(ap)
     mean_ap = sum(classaps) / (len(classnames) - skipped)
     return mean_ap, 100 * np.array(classaps)
+
+
+class GroundTruth:
+    """A Task-1 ground-truth set resident on the device, grouped by segment cls * n_img + img: `gts8` (ng, 8) float64, `gt_off`
+    (nc * n_img + 1,) int32, `difficult` (ng,) uint8, plus `classnames` and `imagenames`.  Records keep their file order inside a
+    segment (np.argmax of voc_eval picks the first maximum in that order)."""
+
+    def __init__(self, gts8, gt_off, difficult, n_img, classnames, imagenames=None):
+        self.gts8, self.gt_off, self.difficult = gts8, gt_off, difficult
+        self.n_img, self.classnames = int(n_img), list(classnames)
+        self.imagenames = list(imagenames) if imagenames is not None else None
+
+    @property
+    def nc(self):
+        return len(self.classnames)
+
+    @classmethod
+    def from_arrays(cls, bbox8, cls_idx, img_idx, difficult, n_img, classnames, imagenames=None, device=None):
+        """Labels held in memory: bbox8 (k, 8), cls_idx / img_idx (k,) integers in [0, len(classnames)) / [0, n_img), difficult (k,)."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("yolov5_obb_amd Task-1 evaluation needs a HIP device (no CPU fallback)")
+        bbox8 = np.ascontiguousarray(bbox8, dtype=np.float64).reshape(-1, 8)
+        c, im = np.asarray(cls_idx, dtype=np.int64).reshape(-1), np.asarray(img_idx, dtype=np.int64).reshape(-1)
+        diff = np.asarray(difficult).reshape(-1) != 0
+        nc, n_img = len(classnames), int(n_img)
+        if not (len(c) == len(im) == len(diff) == len(bbox8)):
+            raise ValueError(f"GroundTruth: {len(bbox8)} boxes, {len(c)} classes, {len(im)} images, {len(diff)} difficult flags")
+        if not 1 <= nc <= 256 or n_img < 0 or nc * n_img >= 2 ** 31:
+            raise ValueError(f"GroundTruth: {nc} classes x {n_img} images is outside what obb_task1_eval_f64 accepts")
+        if len(c) and (c.min() < 0 or c.max() >= nc or im.min() < 0 or im.max() >= n_img):
+            raise ValueError(f"GroundTruth: a record's class is outside [0, {nc}) or its image outside [0, {n_img})")
+        seg = c * n_img + im
+        order = np.argsort(seg, kind="stable")
+        gt_off = np.zeros(nc * n_img + 1, dtype=np.int32)
+        gt_off[1:] = np.cumsum(np.bincount(seg, minlength=nc * n_img))
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        return cls(torch.from_numpy(bbox8[order]).to(dev), torch.from_numpy(gt_off).to(dev),
+                   torch.from_numpy(diff[order].astype(np.uint8)).to(dev), n_img, classnames, imagenames)
+
+    @classmethod
+    def from_files(cls, annopath, imagenames, classnames, device=None):
+        """The labelTxt files of the listed images (annopath.format(imagename)), one native pass per file (obb_task1_parse_gt) --
+        parse_gt for a file that is not the plain layout --, uploaded once.  A record whose name is not in `classnames` is dropped.
+        An image name listed twice raises ValueError: voc_eval keeps such an image's records once in its dict but counts them
+        twice in npos, which an index cannot express."""
+        imagenames, classnames = list(imagenames), list(classnames)
+        if len(set(imagenames)) != len(imagenames):
+            seen = set()
+            twice = [n for n in imagenames if n in seen or seen.add(n)]
+            raise ValueError(f"GroundTruth.from_files: image name listed twice: {twice[0]!r}")
+        cidx = {name: i for i, name in enumerate(classnames)}
+        L = _lib.lib()
+        boxes, cs, ims, diffs = [], [], [], []
+        for i, imagename in enumerate(imagenames):
+            path = annopath.format(imagename)
+            with open(path, 'rb') as f:
+                t = f.read()
+            cap = t.count(b'\n') + 1
+            bbox = np.empty((cap, 8), dtype=np.float64)
+            off, ln, diff = (np.empty(cap, dtype=np.int32) for _ in range(3))
+            k = L.obb_task1_parse_gt(t, len(t), cap, bbox.ctypes.data, off.ctypes.data, ln.ctypes.data, diff.ctypes.data)
+            names = _names(t, off[:k], ln[:k]) if k >= 0 else None
+            if names is None:
+                objs = parse_gt(path)
+                names = [o['name'] for o in objs]
+                bbox = np.array([o['bbox'] for o in objs], dtype=np.float64).reshape(-1, 8)
+                diff = np.array([o['difficult'] for o in objs], dtype=np.int32)
+                k = len(objs)
+            pick = [j for j, name in enumerate(names) if name in cidx]
+            boxes.append(bbox[:k][pick])
+            diffs.append(diff[:k][pick])
+            cs += [cidx[names[j]] for j in pick]
+            ims += [i] * len(pick)
+        bbox8 = np.concatenate(boxes) if boxes else np.zeros((0, 8))
+        return cls.from_arrays(bbox8, cs, ims, np.concatenate(diffs) if diffs else np.zeros(0), len(imagenames), classnames, imagenames, device)
+
+
+def evaluate_rows(rows, gt, ovthresh=0.5, use_07_metric=True, return_curves=False):
+    """`evaluate` on rows held in device memory: rows (nd, >= 11) float64 CUDA, [x1 y1 .. x4 y4, score, cls, src_image] as
+    tile_merge.merge_tiles and detect_large return them (src_image indexes gt.imagenames, cls indexes gt.classnames), gt a
+    GroundTruth on the same device.  Returns (mean_ap, 100 * classaps) like `evaluate`: a class without a detection is skipped the
+    way `evaluate` skips a class without a result file (write_task1 writes none for it), the mean runs over the classes that are
+    not skipped, and no class at all gives (nan, empty array).  return_curves=True adds a dict classname -> (rec, prec), slices
+    of two device tensors in the class's sorted order.  One launch chain (obb_task1_eval_f64) and one copy back (ap, cls_off,
+    npos, info).
+
+    The rows are evaluated WITH THE VALUES THEY CARRY.  mergesingle's second rounding -- round(conf, 2) and round(coord, 1),
+    ResultMerge_multi_process.py:218-233 -- happens only in the text that write_task1 prints; write_task1 + evaluate therefore
+    remains the way to get the file pipeline's number.  Order inside a class: score descending, equal scores in ascending row
+    (np.argsort(-confidence, kind='stable')); at two decimals the text is full of ties, and the reference's own AP then depends
+    on the order numpy's unstable sort happens to leave them in."""
+    _lib.require_cuda(rows, "rows")
+    if rows.dim() != 2 or rows.shape[1] < 11 or rows.dtype != torch.float64:
+        raise RuntimeError(f"evaluate_rows: rows must be (n, >= 11) float64, got {tuple(rows.shape)} {rows.dtype}")
+    if not isinstance(gt, GroundTruth):
+        raise TypeError(f"evaluate_rows: gt must be a GroundTruth, got {type(gt)}")
+    dev = rows.device
+    if gt.gts8.device != dev:
+        raise RuntimeError(f"evaluate_rows: rows are on {dev}, the ground truth is on {gt.gts8.device}")
+    nd, nc, ng = int(rows.shape[0]), gt.nc, int(gt.gts8.shape[0])
+    if rows.stride(1) != 1 or (nd > 1 and rows.stride(0) < 11):
+        rows = rows.contiguous()
+    stride = int(rows.stride(0)) if nd > 1 else int(rows.shape[1])          # (a slice of wider rows is passed as it is)
+    L = _lib.lib()
+    with _lib.guard(dev):
+        # ap (nc) float64 | npos (nc) int64 | cls_off (nc + 1) int32 | info (2) int32, one buffer, one copy
+        n_off = (nc + 2) // 2
+        tail = torch.empty(2 * nc + n_off + 1, dtype=torch.int64, device=dev)
+        base = tail.data_ptr()
+        rec = torch.empty(nd, dtype=torch.float64, device=dev) if return_curves else None
+        prec = torch.empty(nd, dtype=torch.float64, device=dev) if return_curves else None
+        need = L.obb_task1_eval_workspace_bytes(nd, ng, gt.n_img, nc)
+        if need == 0:
+            raise RuntimeError(f"evaluate_rows: nd = {nd}, ng = {ng}, n_img = {gt.n_img}, nc = {nc} is outside what obb_task1_eval_f64 accepts")
+        ws = _lib.workspace(need, dev)
+        rc = L.obb_task1_eval_f64(_lib.ptr(rows), stride, nd, _lib.ptr(gt.gts8), _lib.ptr(gt.gt_off), _lib.ptr(gt.difficult), ng, gt.n_img, nc,
+                                  float(ovthresh), 1 if use_07_metric else 0, C.c_void_p(base), C.c_void_p(base + 8 * nc),
+                                  C.c_void_p(base + 16 * nc), C.c_void_p(0), _lib.ptr(rec), _lib.ptr(prec),
+                                  C.c_void_p(base + 8 * (2 * nc + n_off)), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, "obb_task1_eval_f64")
+        tail_h = tail.cpu().numpy()
+    info = tail_h[2 * nc + n_off:].view(np.int32)
+    if info[0]:
+        raise RuntimeError(f"evaluate_rows: a row's class is not an integer in [0, {nc}) or its image not one in [0, {gt.n_img})")
+    ap = tail_h[:nc].view(np.float64)
+    cls_off = tail_h[2 * nc:2 * nc + n_off].view(np.int32)[:nc + 1]
+    have = np.flatnonzero(np.diff(cls_off) > 0)
+    classaps = [float(ap[c]) for c in have]
+    mean_ap = sum(classaps) / len(classaps) if classaps else float('nan')
+    if not return_curves:
+        return mean_ap, 100 * np.array(classaps)
+    curves = {gt.classnames[c]: (rec[cls_off[c]:cls_off[c + 1]], prec[cls_off[c]:cls_off[c + 1]]) for c in have}
+    return mean_ap, 100 * np.array(classaps), curves

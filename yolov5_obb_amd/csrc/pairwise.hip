@@ -346,6 +346,20 @@ __global__ __launch_bounds__(64) void k_eval_best_gt_hbb(const double* __restric
 
 }  // namespace obb
 
+#include "task1_eval.h"
+
+namespace obb {
+
+int launch_eval_best_gt(const double* dets8, const int32_t* det_img, int64_t nd, const double* gts8, const int32_t* gt_off,
+                        double* ovmax, int32_t* jmax, hipStream_t st) {
+  int64_t nb = (nd + kEvalWaves - 1) / kEvalWaves;
+  if (nb > 256 * 16) nb = 256 * 16;
+  k_eval_best_gt<<<(unsigned)nb, 64 * kEvalWaves, 0, st>>>(dets8, det_img, nd, gts8, gt_off, ovmax, jmax);
+  return hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH;
+}
+
+}  // namespace obb
+
 using namespace obb;
 
 #define OBB_CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? OBB_OK : OBB_ERR_LAUNCH)
@@ -386,10 +400,19 @@ int obb_eval_best_gt_f64(const double* dets8, const int32_t* det_img, int64_t nd
                          int64_t n_img, double* ovmax, int32_t* jmax, void* stream) {
   if (nd < 0 || n_img < 0 || (nd > 0 && (!dets8 || !det_img || !gt_off || !ovmax || !jmax))) return OBB_ERR_BAD_ARG;
   if (nd == 0) return OBB_OK;
-  int64_t nb = (nd + kEvalWaves - 1) / kEvalWaves;
-  if (nb > 256 * 16) nb = 256 * 16;
-  k_eval_best_gt<<<(unsigned)nb, 64 * kEvalWaves, 0, (hipStream_t)stream>>>(dets8, det_img, nd, gts8, gt_off, ovmax, jmax);
-  return OBB_CHECK_LAUNCH();
+  return launch_eval_best_gt(dets8, det_img, nd, gts8, gt_off, ovmax, jmax, (hipStream_t)stream);
+}
+
+size_t obb_task1_eval_workspace_bytes(int64_t nd, int64_t ng, int64_t n_img, int64_t nc) {
+  return t1_args_ok(11, nd, ng, n_img, nc) ? t1_layout(nullptr, nd, ng, nc).bytes : 0;
+}
+
+int obb_task1_eval_f64(const double* dets, int64_t det_stride, int64_t nd, const double* gts8, const int32_t* gt_off,
+                       const uint8_t* difficult, int64_t ng, int64_t n_img, int64_t nc, double ovthresh, int flags, double* ap,
+                       int64_t* npos, int32_t* cls_off, int32_t* order, double* rec, double* prec, int32_t* info, void* ws,
+                       size_t ws_extent, void* stream) {
+  return run_task1_eval(dets, det_stride, nd, gts8, gt_off, difficult, ng, n_img, nc, ovthresh, flags, ap, npos, cls_off, order, rec, prec,
+                        info, ws, ws_extent, (hipStream_t)stream);
 }
 
 int obb_eval_best_gt_hbb_f64(const double* dets4, int64_t det_stride, const int32_t* det_img, int64_t nd, const double* gts4,
